@@ -226,7 +226,10 @@ int vds_run(vds_handle *h, int32_t n_ticks);
  * submission per call instead of three or four launches per slot.  The replicas run as the groups of vds_run in parallel branches
  * (the observation and dispatch kernels of one group under the tick of another); the policy node joins them once per slot.
  * Results are those of the stepwise loop.  Asynchronous on the handle's stream, which must be the stream the policy was
- * captured on, or ordered with it.  Errors of skipped actions surface at the next vds_sync as for vds_apply_dispatch_device. */
+ * captured on, or ordered with it.  Errors of skipped actions surface at the next vds_sync as for vds_apply_dispatch_device.
+ * `planes`: bits 0-4 the observation planes of vds_obs_device_planes; bit 5 (VDS_PLANE_OUTCOMES) adds the slot's per-cluster order
+ * outcomes to the block of vds_outcomes_device, every slot, before the policy node. */
+#define VDS_PLANE_OUTCOMES 32
 int vds_run_hooked(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph);
 
 /* The graph of vds_run_hooked is keyed by what it was built for: first slot, slot count, planes, K, the ADDRESSES of the action
@@ -317,6 +320,25 @@ int vds_reduce_counters(vds_handle *h, int64_t *out, void **dev_ptr);
  *    UpdateFunction, DispatchNum, TotallyDispatchCost}
  * (matched = OrderNum - RejectNum).  Asynchronous; overwritten by the next counter call. */
 int vds_counters_device(vds_handle *h, void **dev_ptr);
+
+/* How each cluster's orders fared in the slot stepped last - what RewardFunction (:999-1004) sees in `for c in self.Clusters: for o
+ * in c.Orders` while Cluster.Orders still holds the slot's orders (filled :919, cleared :1013).  Element (replica r, cluster c)
+ * covers the orders whose pickup node lies in cluster c that MatchFunction processed in that slot, whichever cluster's vehicle
+ * served them (neighbour search :978-996 included); the order that is never processed (quirk Q1, :914-915) is in none.  Four int64
+ * planes [4][R][C], replicas in the caller's order:
+ *   0 served     orders with ArriveInfo == "Success"                  (:965)
+ *   1 rejected   orders with ArriveInfo == "Reject"                   (:945, :969)
+ *   2 wait_sum   sum of PickupWaitTime of the served orders           (:949, :952)
+ *   3 value_sum  sum of OrderValue of the served orders (matched only, like word 3 of vds_counters_device; :341-342)
+ * Summed over clusters and slots they are the replica's matched orders, RejectNum, TotallyWaitTime and matched value.  A replica
+ * whose order day is over at that slot (vds_load_order_days) reads zeros; dispatch does not change them.  Before the first step
+ * of an episode: zeros.  VDS_EINVAL before vds_reset.
+ * vds_outcomes_device computes the block asynchronously on the handle's stream and returns its device address: made on the first
+ * call, fixed until the tables are re-made (vds_load_orders* with other sizes, vds_set_idle_cap, vds_set_replica_days, vds_destroy).
+ * No tick, vds_run or vds_run_hooked without VDS_PLANE_OUTCOMES computes it.
+ * vds_read_outcomes: the same, copied to the host (synchronous), each [R*C] replica-major; any pointer may be NULL. */
+int vds_outcomes_device(vds_handle *h, void **dev_ptr);
+int vds_read_outcomes(vds_handle *h, int64_t *served, int64_t *rejected, int64_t *wait_sum, int64_t *value_sum);
 
 /* As vds_reduce_counters, delivering the int64 [VDS_NUM_COUNTERS] totals of this handle's
  * replicas (raw device sums; VALUE_SUM = matched orders only) into caller-owned DEVICE memory,

@@ -76,6 +76,8 @@ SYMBOLS = {
     "vds_run_hooked_invalidate": (C.c_int, [_VP]),
     "vds_supply_inplace": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_VP), C.POINTER(_I32)]),
     "vds_counters_device": (C.c_int, [_VP, C.POINTER(_VP)]),
+    "vds_outcomes_device": (C.c_int, [_VP, C.POINTER(_VP)]),
+    "vds_read_outcomes": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "vds_read_counters": (C.c_int, [_VP, _VP]),
     "vds_reduce_counters": (C.c_int, [_VP, _VP, C.POINTER(_VP)]),
     "vds_reduce_counters_into": (C.c_int, [_VP, _VP]),

@@ -59,6 +59,8 @@ void emit_tick_dense(const Emit &, const Static &, const State &, int, int, int)
 void emit_dense_flush(const Emit &, const Static &, const State &, int, int);
 void emit_pack_obs(const Emit &, const Static &, const State &, int, int, int, int *, int, int);
 void emit_dispatch_dense(const Emit &, const Static &, const State &, int, int, const int *, int, int, int);
+void emit_slot_outcomes(const Emit &, const Static &, const State &, int, int, long long *, int, int);
+void launch_slot_outcomes(const Static &, const State &, int, int, long long *, hipStream_t);
 }  // namespace vds
 
 using namespace vds;
@@ -233,6 +235,7 @@ struct vds_handle {
     int *d_veh_stage = nullptr;              // vds_reset: the caller's start nodes land here and are checked on the device before they
     unsigned long long *d_bad = nullptr;     // replace d_veh_node (index of the first node outside every cluster, ~0 if none)
     int *d_obs = nullptr;
+    long long *d_outc = nullptr;             // vds_outcomes_device: int64 [4][R_ext][C], made on the first request (in state_allocs)
     long long *d_cnt_per = nullptr, *d_cnt_tot = nullptr;
     int *d_actions = nullptr;
     size_t actions_cap = 0;
@@ -268,6 +271,7 @@ struct vds_handle {
     void *hook_policy_inst = nullptr;
     int hook_t0 = -1, hook_n = 0, hook_G = 1, hook_planes = 0, hook_K = 0;
     unsigned hook_gen = 0;
+    const long long *hook_outc = nullptr;
     const void *hook_actions = nullptr;
     void *hook_policy = nullptr;
     hipStream_t hook_stream = nullptr;
@@ -931,6 +935,7 @@ static int alloc_state(vds_handle *h, int O) {
         return VDS_OK;                                   // another day on the same handle: the state tables still fit
     for (void *p : h->state_allocs) dev_free(p);
     h->state_allocs.clear();
+    h->d_outc = nullptr;                                 // (the outcome block lived there: made again on the next request)
     S.idle_cap = idle_cap; S.fl_cap = far_cap; S.in_cap = far_cap; S.H = H; S.ring_cap = ring_cap;
     const size_t B = (size_t)C * R;
     h->alloc_dense = S.dense; h->alloc_st = S.dense_st;
@@ -2129,6 +2134,8 @@ int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger) {
 // one submission per call instead of three or four launches per slot, and - like vds_run - the replicas as groups in parallel
 // branches, so that the small latency-bound kernels of one group (observations, dispatch) run under the tick of the other.  The
 // policy node, which sees all replicas, joins the branches once per slot.
+static int ensure_outcomes(vds_handle *h);
+
 static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
     if (policy_graph && h->hook_policy_inst != policy_graph) {
         if (h->hook_policy_exec) { (void)hipStreamSynchronize(h->stream); (void)hipGraphExecDestroy(h->hook_policy_exec); h->hook_policy_exec = nullptr; }
@@ -2138,7 +2145,8 @@ static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int3
     for (int i = 0; i < n_ticks; ++i) {
         int rc = vds_step(h);
         if (rc) return rc;
-        if (planes && (rc = vds_obs_device_planes(h, planes, nullptr))) return rc;
+        if ((planes & 31) && (rc = vds_obs_device_planes(h, planes & 31, nullptr))) return rc;
+        if ((planes & VDS_PLANE_OUTCOMES) && (rc = vds_outcomes_device(h, nullptr))) return rc;
         if (policy_graph) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
         if (K > 0 && dev_actions && (rc = vds_apply_dispatch_device(h, K, dev_actions))) return rc;
         if ((rc = vds_advance(h))) return rc;
@@ -2148,12 +2156,13 @@ static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int3
 
 static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_run_hooked: call vds_reset first");
-    if (n_ticks < 0 || planes < 0 || planes > 31 || K < 0 || K > 64 || (K > 0 && !dev_actions))
-        return fail(h, VDS_EINVAL, "vds_run_hooked: planes is a mask of the five planes (0 .. 31), K in [0, 64] with a non-null action tensor");
+    if (n_ticks < 0 || planes < 0 || planes > 63 || K < 0 || K > 64 || (K > 0 && !dev_actions))
+        return fail(h, VDS_EINVAL, "vds_run_hooked: planes is a mask of the five observation planes and VDS_PLANE_OUTCOMES (0 .. 63), K in [0, 64] with a non-null action tensor");
     if (h->last_stepped == h->t) return fail(h, VDS_EINVAL, "vds_run_hooked: tick %d already stepped; call vds_advance", h->t);
     if (h->t + n_ticks > h->S.T) return fail(h, VDS_EINVAL, "vds_run_hooked: %d slots from slot %d on run past the end of the day (%d slots, :1048)", n_ticks, h->t, h->S.T);
     if (n_ticks == 0) return VDS_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (planes & VDS_PLANE_OUTCOMES) { const int rco = ensure_outcomes(h); if (rco) return rco; }
     if (h->use_graph < 0) { const char *v = getenv("VDS_RUN_GRAPH"); h->use_graph = (v && *v == '0') ? 0 : 1; }
     const bool groupable = run_groups_hybrid(h) || run_groups_plain(h);
     if (!h->use_graph || h->profiling || !groupable) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
@@ -2165,7 +2174,7 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     (void)run_group_count(h);
     const int G = h->run_groups > 0 ? std::min(run_group_count(h), RUN_GROUPS_MAX) : 1;
     const bool same = h->hook_exec && h->hook_gen == h->tables_gen && h->hook_t0 == h->t && h->hook_n == n_ticks && h->hook_G == G && h->hook_planes == planes && h->hook_K == K &&
-                      h->hook_actions == dev_actions && h->hook_policy == policy_graph && h->hook_stream == h->stream;
+                      h->hook_actions == dev_actions && h->hook_policy == policy_graph && h->hook_stream == h->stream && h->hook_outc == h->d_outc;
     if (!same) {
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
@@ -2200,11 +2209,18 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                 }
                 if (err != hipSuccess) break;
                 chain = n1;
-                if (planes) {
-                    e.deps = &n1; e.ndeps = 1; e.node = &n3;
-                    emit_pack_obs(e, h->S, h->D, t, 1, planes, h->d_obs, r_lo, r_n);
+                if (planes & 31) {
+                    e.deps = &chain; e.ndeps = 1; e.node = &n3;
+                    emit_pack_obs(e, h->S, h->D, t, 1, planes & 31, h->d_obs, r_lo, r_n);
                     if (err != hipSuccess) break;
                     chain = n3;
+                }
+                if (planes & VDS_PLANE_OUTCOMES) {          // the slot's per-cluster order outcomes, behind the group's last tick launch
+                    hipGraphNode_t n4 = nullptr;
+                    e.deps = &chain; e.ndeps = 1; e.node = &n4;
+                    emit_slot_outcomes(e, h->S, h->D, t, 1, h->d_outc, r_lo, r_n);
+                    if (err != hipSuccess) break;
+                    chain = n4;
                 }
             }
             if (err != hipSuccess) break;
@@ -2238,7 +2254,7 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
             return fail(h, VDS_EHIP, "vds_run_hooked: building the day graph failed: %s", hipGetErrorString(err));
         }
         bool updated = false;
-        if (h->hook_exec && h->hook_n == n_ticks && h->hook_G == G && (h->hook_planes != 0) == (planes != 0) && (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr)) {
+        if (h->hook_exec && h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) && (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr)) {
             (void)hipStreamSynchronize(h->hook_stream);
             hipGraphNode_t bad = nullptr;
             hipGraphExecUpdateResult res;
@@ -2255,7 +2271,7 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
         }
         (void)hipGraphDestroy(g);
         h->hook_t0 = h->t; h->hook_n = n_ticks; h->hook_G = G; h->hook_planes = planes; h->hook_K = K; h->hook_actions = dev_actions;
-        h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen;
+        h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen; h->hook_outc = h->d_outc;
     }
     HIPCHK(h, hipGraphLaunch(h->hook_exec, h->stream));
     h->t += n_ticks;
@@ -2461,6 +2477,49 @@ int vds_counters_device(vds_handle *h, void **dev_ptr) {
     HIPCHK(h, hipGetLastError());
     *dev_ptr = h->d_cnt_per;
     return VDS_OK;
+}
+
+// Per-cluster order outcomes of the slot stepped last (RewardFunction's view of Cluster.Orders, :999-1004): k_slot_outcomes into the
+// int64 [4][R_ext][C] block, made on the first request (it lives with the state tables: re-made when they are).
+static int ensure_outcomes(vds_handle *h) {
+    if (h->d_outc) return VDS_OK;
+    struct Sink { vds_handle *h; std::vector<void *> *old; ~Sink() { h->alloc_sink = old; } } sink{h, h->alloc_sink};
+    h->alloc_sink = &h->state_allocs;
+    const size_t n = 4 * (size_t)h->R_ext * h->S.C;
+    const int rc = dev_alloc(h, &h->d_outc, n);
+    if (rc) { h->d_outc = nullptr; return rc; }
+    HIPCHK(h, hipMemsetAsync(h->d_outc, 0, n * sizeof(long long), h->stream));
+    return VDS_OK;
+}
+
+static int outcomes_device_impl(vds_handle *h, void **dev_ptr) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_outcomes_device: call vds_reset first");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int rc = ensure_outcomes(h);
+    if (rc) return rc;
+    if (h->last_stepped < 0) HIPCHK(h, hipMemsetAsync(h->d_outc, 0, 4 * (size_t)h->R_ext * h->S.C * sizeof(long long), h->stream));
+    else launch_slot_outcomes(h->S, h->D, h->last_stepped, 1, h->d_outc, h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (dev_ptr) *dev_ptr = h->d_outc;
+    return VDS_OK;
+}
+
+int vds_outcomes_device(vds_handle *h, void **dev_ptr) {
+    return guarded(h, "vds_outcomes_device", [&] { return outcomes_device_impl(h, dev_ptr); });
+}
+
+static int read_outcomes_impl(vds_handle *h, int64_t *served, int64_t *rejected, int64_t *wait_sum, int64_t *value_sum) {
+    const int rc = outcomes_device_impl(h, nullptr);
+    if (rc) return rc;
+    const size_t RC = (size_t)h->R_ext * h->S.C;
+    int64_t *dst[4] = {served, rejected, wait_sum, value_sum};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k]) HIPCHK(h, hipMemcpyAsync(dst[k], h->d_outc + k * RC, RC * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    return vds_sync(h);
+}
+
+int vds_read_outcomes(vds_handle *h, int64_t *served, int64_t *rejected, int64_t *wait_sum, int64_t *value_sum) {
+    return guarded(h, "vds_read_outcomes", [&] { return read_outcomes_impl(h, served, rejected, wait_sum, value_sum); });
 }
 
 static int read_counters_impl(vds_handle *h, int64_t *out) {

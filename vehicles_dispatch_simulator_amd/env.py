@@ -13,6 +13,8 @@ import numpy as np
 from . import _lib
 
 PICKUP_REJECT_THRESHOLD = 600_000_000_000   # int(config/setting.py:7 PICKUPTIMEWINDOW), quirk Q3
+PLANE_OUTCOMES = 32                         # vds_run_hooked plane bit of the per-cluster order outcomes (VDS_PLANE_OUTCOMES)
+OUTCOME_NAMES = ("served", "rejected", "wait_sum", "value_sum")
 
 
 def _p(a: Optional[np.ndarray]):
@@ -228,13 +230,16 @@ class BatchedDispatchEnv:
     def run(self, n_ticks: int):
         self._chk(self._lib.vds_run(self._h, int(n_ticks)))
 
-    def run_hooked(self, n_ticks: int, actions=None, policy_graph=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False):
+    def run_hooked(self, n_ticks: int, actions=None, policy_graph=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False,
+                   outcomes=False):
         """``n_ticks`` slots of ``SimCity`` WITH the dispatch hook on the device as one graph launch (``vds_run_hooked``): per slot
-        step -> the named observation planes into the block ``obs_torch`` returns -> ``policy_graph`` -> ``actions`` applied ->
+        step -> the named observation planes into the block ``obs_torch`` returns (``outcomes=True``: also the slot's per-cluster
+        order outcomes into the block ``outcomes_torch`` returns) -> ``policy_graph`` -> ``actions`` applied ->
         advance.  ``actions``: the contiguous int32 CUDA tensor ``[R, K, 3]`` the policy writes (``None``: no dispatch).
         ``policy_graph``: a ``torch.cuda.CUDAGraph`` captured with ``keep_graph=True`` (its ``raw_cuda_graph()`` is embedded), or a
         raw ``hipGraph_t`` as an integer, or ``None`` (the tensor is applied as it stands)."""
         planes = (1 if idle_pre else 0) | (2 if idle_now else 0) | (4 if supply else 0) | (8 if cl_orders else 0) | (16 if inflight else 0)
+        planes |= PLANE_OUTCOMES if outcomes else 0
         K, ptr = 0, None
         if actions is not None:
             if tuple(actions.shape[:1]) != (self.R,) or actions.dim() != 3 or actions.shape[2] != 3:
@@ -365,6 +370,33 @@ class BatchedDispatchEnv:
         blk = _Block()
         blk.__cuda_array_interface__ = {"shape": (self.R, 8), "typestr": "<i8", "data": (p.value, False), "version": 2, "strides": None}
         return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+
+    def outcomes_device_ptr(self) -> int:
+        """Device pointer of the int64 ``[4][R][C]`` outcome block, computed for the slot stepped last (``vds_outcomes_device``)."""
+        p = C.c_void_p()
+        self._chk(self._lib.vds_outcomes_device(self._h, C.byref(p)))
+        return p.value
+
+    def outcomes_torch(self):
+        """How each cluster's orders fared in the slot stepped last, as a zero-copy ``torch`` int64 tensor ``[4, R, C]`` on the GPU:
+        ``served`` (``ArriveInfo == "Success"``), ``rejected`` (``"Reject"``), ``wait_sum`` (``PickupWaitTime`` of the served) and
+        ``value_sum`` (``OrderValue`` of the served) over the orders that ``Cluster.Orders`` holds during the slot's hooks
+        (``simulator.py:919-1013``).  Aliases library memory, overwritten by the next outcome call or by ``run_hooked(outcomes=True)``."""
+        import torch
+
+        class _Block:
+            pass
+
+        blk = _Block()
+        blk.__cuda_array_interface__ = {"shape": (4, self.R, self.C), "typestr": "<i8", "data": (self.outcomes_device_ptr(), False),
+                                        "version": 2, "strides": None}
+        return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+
+    def outcomes(self) -> Dict[str, np.ndarray]:
+        """``outcomes_torch`` copied to the host: ``{served, rejected, wait_sum, value_sum}``, each int64 ``[R, C]``."""
+        arrs = [np.empty((self.R, self.C), dtype=np.int64) for _ in OUTCOME_NAMES]
+        self._chk(self._lib.vds_read_outcomes(self._h, *[_p(a) for a in arrs]))
+        return dict(zip(OUTCOME_NAMES, arrs))
 
     def counters(self) -> np.ndarray:
         out = np.zeros((self.R, _lib.NUM_COUNTERS), dtype=np.int64)

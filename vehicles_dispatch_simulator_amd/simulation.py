@@ -27,7 +27,10 @@ What a maintainer should know (also in INTEGRATION.md):
     The object views (``Clusters`` / ``Vehicles`` / ``Orders``) of replica ``Replica`` are refreshed once, after the day;
   * ``BatchedHooks=True`` with ``BatchedPolicy(obs)`` overridden (and no per-slot Python hook): the policy is captured ONCE as a
     graph and the whole day - per slot Update + Match + SupplyExpect, observation planes, policy, dispatch, next slot
-    (:1048-1091) - is ONE graph launch (``vds_run_hooked``); see ``BatchedPolicy``.
+    (:1048-1091) - is ONE graph launch (``vds_run_hooked``); see ``BatchedPolicy``;
+  * ``BatchedOutcomes=True`` (with ``BatchedHooks=True``): ``self.BatchedOutcomes`` holds how each cluster's orders fared in the
+    slot - ``served`` / ``rejected`` / ``wait_sum`` / ``value_sum`` over ``Cluster.Orders`` (:919-1013), CUDA int64 tensors
+    ``[Replicas, clusters]`` - refreshed every slot before ``RewardFunction``; ``BatchedPolicy`` receives the same four keys.
 """
 from __future__ import annotations
 
@@ -78,7 +81,8 @@ class _RoadCostMap(object):
 class Simulation(object):
     def __init__(self, ClusterMode, DemandPredictionMode, DispatchMode, VehiclesNumber, TimePeriods, LocalRegionBound,
                  SideLengthMeter, VehiclesServiceMeter, NeighborCanServer, FocusOnLocalRegion,
-                 Replicas=1, Replica=0, Device=0, VehicleSeed=None, DataDir=None, Quiet=False, BatchedHooks=False, **device_kwargs):
+                 Replicas=1, Replica=0, Device=0, VehicleSeed=None, DataDir=None, Quiet=False, BatchedHooks=False, BatchedOutcomes=False,
+                 **device_kwargs):
         # components (simulator.py:44-45)
         self.DispatchModule = None
         self.DemandPredictorModule = None
@@ -130,6 +134,10 @@ class Simulation(object):
         self.Quiet = Quiet
         self.BatchedHooks = bool(BatchedHooks)
         self.BatchedObs = None
+        if BatchedOutcomes and not self.BatchedHooks:
+            raise Exception("BatchedOutcomes needs BatchedHooks=True (the planes are device tensors over all Replicas)")
+        self._outcomes_on = bool(BatchedOutcomes)
+        self.BatchedOutcomes = None         # BatchedOutcomes=True: {served, rejected, wait_sum, value_sum} of the slot, CUDA int64 [Replicas, clusters]
         if self.BatchedHooks and "stream" not in device_kwargs:
             import torch          # the policy's tensors and the engine's launches share torch's current stream
             cs = torch.cuda.current_stream(int(Device)).cuda_stream
@@ -607,15 +615,31 @@ class Simulation(object):
     def _policy_obs(self):
         planes = dict((k, k in self.BatchedPolicyPlanes) for k in ("idle_pre", "idle_now", "supply", "cl_orders", "inflight"))
         blk = self.env.obs_torch(**planes)              # the library's block: fixed address, rewritten by every slot's observation pass
-        return {k: blk[i] for i, k in enumerate(("idle_pre", "idle_now", "supply", "cl_orders", "inflight")) if planes[k]}, planes
+        obs = {k: blk[i] for i, k in enumerate(("idle_pre", "idle_now", "supply", "cl_orders", "inflight")) if planes[k]}
+        if self._outcomes_on:                           # (the outcome block: fixed address, rewritten by every slot of the day graph)
+            obs.update(self._outcome_views())
+            planes = dict(planes, outcomes=True)
+        return obs, planes
+
+    def _outcome_views(self):
+        blk = self.env.outcomes_torch()
+        return {k: blk[i] for i, k in enumerate(("served", "rejected", "wait_sum", "value_sum"))}
+
+    def _outcome_block_ptr(self):
+        return self.env.outcomes_device_ptr() if self._outcomes_on else None
 
     def _policy_day_graph(self):
         """The captured policy for this handle (made on first use): (actions tensor, graph, planes) or None when it cannot be
         captured (the reason is kept in ``self.BatchedPolicyGraphError``; the caller then runs slot by slot)."""
         import torch
         st = getattr(self, "_bp_state", None)
-        if st is not None and st["env"] is self.env:
+        # (keyed by the outcome block's address too: a Reload that re-makes the state tables moves it, and a captured policy must not
+        # go on reading the freed block)
+        outc = self._outcome_block_ptr()
+        if st is not None and st["env"] is self.env and st.get("outc") == outc:
             return st if st["graph"] is not None else None        # (a capture that failed on this handle is not tried again)
+        if st is not None and st["env"] is self.env:
+            self.env.run_hooked_invalidate()                      # (the day graph embeds the policy captured before)
         self.BatchedPolicyGraphError = None
         obs, planes = self._policy_obs()
         try:
@@ -638,9 +662,9 @@ class Simulation(object):
                 acts.copy_(self.BatchedPolicy(obs))
         except Exception as e:
             self.BatchedPolicyGraphError = repr(e)
-            self._bp_state = dict(env=self.env, graph=None)
+            self._bp_state = dict(env=self.env, outc=outc, graph=None)
             return None
-        self._bp_state = dict(env=self.env, obs=obs, planes=planes, actions=acts, graph=g)
+        self._bp_state = dict(env=self.env, outc=outc, obs=obs, planes=planes, actions=acts, graph=g)
         return self._bp_state
 
     def _hooks_overridden(self):
@@ -739,6 +763,8 @@ class Simulation(object):
             st = self._policy_day_graph()
             T = self.env.T
             self.BatchedObs = st["obs"]
+            if self._outcomes_on:
+                self.BatchedOutcomes = {k: st["obs"][k] for k in ("served", "rejected", "wait_sum", "value_sum")}
             self.BatchedPolicyBegin()
             t = dt.datetime.now()
             self.env.run_hooked(T, actions=st["actions"], policy_graph=st["graph"], **st["planes"])
@@ -761,6 +787,8 @@ class Simulation(object):
                 t = dt.datetime.now(); self.env.step(); self.TotallyMatchTime += dt.datetime.now() - t     # Update + Match + SupplyExpect
                 ob = self.env.obs_torch()
                 self.BatchedObs = {k: ob[i] for i, k in enumerate(names)}
+                if self._outcomes_on:
+                    self.BatchedOutcomes = self._outcome_views()
                 t = dt.datetime.now(); self.RewardFunction(); self.TotallyRewardTime += dt.datetime.now() - t
                 t = dt.datetime.now(); self.GetNextStateFunction(); self.TotallyNextStateTime += dt.datetime.now() - t
                 t = dt.datetime.now(); self.LearningFunction(); self.TotallyLearningTime += dt.datetime.now() - t
