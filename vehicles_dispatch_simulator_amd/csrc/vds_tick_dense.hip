@@ -89,6 +89,8 @@ struct DenseArgs {
     const int4 *tdesc;               // (one shared day) per-bucket descriptors, Static.tdesc
     // stamp form (ST: neighbour search on the dense layout, vds_device.h Static.dense_st)
     unsigned short *stamp; int *dry; int *slow_tick; const int *so_rank;
+    int slow_T;                      // slots of the slow_tick plane ([slow_T][C])
+    const int2 *bmap;                // (k_tick_dense_mixed) the slot's block map: one {cluster in the LPT order, (row0 - r_lo) << 1 | form} per workgroup
     int *sup, *sup_slot;             // SupplyExpect in place (State.sup): planes by arrival slot
     const Static *Sdev; const State *Ddev;
 };
@@ -1105,8 +1107,10 @@ __device__ __forceinline__ void dense_body(const DenseArgs &S, const DenseArgs &
 // block / order records / candidate records staged once for twice the rows, and the prologue's chain of dependent loads - the
 // largest part of the kernel, profiles/r04/r04_ablate_dense.txt - paid once per 32 rows)
 // ST: stamp form - Update + own-cluster matching of the neighbour-search tick on the dense layout (dense_body; Static.dense_st)
-template <bool U8, int DM, int LPR, bool PULL, int TABMAX = DN_TAB, int ROWS = DN_ROWS, bool ST = false>
-__global__ __launch_bounds__(ROWS * LPR, TABMAX > 128 ? DN_MIN_WAVES256 : (LPR == 16 ? DN_MIN_WAVES16 : (LPR == 8 ? DN_MIN_WAVES8 : DN_MIN_WAVES4))) void k_tick_dense(DenseArgs P, int t) {
+// The body of one workgroup: cluster ci of the slot's longest-processing-time-first order (Static.tdesc), rows [row0, row0 + ROWS);
+// tabl: the longest list the fast path takes (DenseArgs.dense_tab of the form; at most TABMAX)
+template <bool U8, int DM, int LPR, bool PULL, int TABMAX, int ROWS, bool ST>
+__device__ __forceinline__ void tick_dense_wg(const DenseArgs &P, int t, int ci, int row0, int tabl) {
     static_assert(TABMAX == 128 || (TABMAX == 256 && LPR == 16 && U8), "256-entry tables: 16 lanes per replica, byte costs");
     static_assert(!ST || (U8 && DM == 0 && PULL), "stamp form: byte costs, one shared day, static arrival slots");
     static_assert(ROWS == DN_ROWS || (ROWS == 32 && DM == 0 && LPR == 8) || ((ROWS == 8 || ROWS == 4) && DM == 1 && LPR == 16),
@@ -1131,18 +1135,15 @@ __global__ __launch_bounds__(ROWS * LPR, TABMAX > 128 ? DN_MIN_WAVES256 : (LPR =
     int2 *lds_drec = reinterpret_cast<int2 *>(lds_rank + (ST ? DN_ORDERS : 0));
     unsigned *tab_all = reinterpret_cast<unsigned *>(lds_drec + (PULL ? DN_CAND : 0));
     CT *lds_blk = reinterpret_cast<CT *>(tab_all + ROWS * (TABMAX + DN_TPAD));
-    // longest-processing-time-first: all replica chunks of the biggest cluster lead the grid
-    const int nchunks = gridDim.x / S.C;
     // {n_c, byte offset of the block, cluster, 0}.  One shared day: the cluster's descriptor sits BEHIND the bucket's in Static.tdesc
     // (32 bytes per (slot, cluster)): ONE scalar load - two loads from two tables were issued one after the other (the second
     // waited for a register of the first: ISA of round 4), a dependent round trip at the head of every workgroup
     int4 cd, td0 = make_int4(0, 0, 0, 0);
     if (DM == 0) {
-        const int4 *tp = S.tdesc + 2 * ((size_t)t * S.C + blockIdx.x / nchunks);
+        const int4 *tp = S.tdesc + 2 * ((size_t)t * S.C + ci);
         td0 = tp[0]; cd = tp[1];
-    } else cd = S.cdesc_dense[blockIdx.x / nchunks];
+    } else cd = S.cdesc_dense[ci];
     const int c = cd.z, nc = cd.x;
-    const int row0 = S.r_lo + (int)(blockIdx.x % nchunks) * ROWS;      // (vds_run launches the tick per replica group: rows [r_lo, r_hi))
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = lane_id();
     const int g = lane / LPR, lg = lane & (LPR - 1);
@@ -1311,11 +1312,11 @@ __global__ __launch_bounds__(ROWS * LPR, TABMAX > 128 ? DN_MIN_WAVES256 : (LPR =
     __syncthreads();
     PROF_STAMP_NW(1);       // barrier
     const int mnew0 = ST ? max(m + A, m_raw) : m + A;          // (stamp form: the raw list passes through the table as well)
-    const bool bad = rowvalid && (!wg_ok || far != 0 || Aring > S.dense_keys || Aring > S.ring_cap || A > DN_TAB || mnew0 > min(S.dense_tab, TABMAX) || mnew0 > S.idle_cap || S.dense_force_slow ||
+    const bool bad = rowvalid && (!wg_ok || far != 0 || Aring > S.dense_keys || Aring > S.ring_cap || A > DN_TAB || mnew0 > min(tabl, TABMAX) || mnew0 > S.idle_cap || S.dense_force_slow ||
                                   (PULL && (A - Aring > S.dense_keys * 2 || A > DN_TH)));
 #ifdef VDS_PROF
     if (bad && lg == 0) {       // why the row leaves the fast path (first reason that applies): vds_debug_read_err [4..11]
-        const int why = k > DN_ORDERS ? 4 : (n > DN_CAND ? 5 : (far != 0 ? 6 : ((Aring > S.dense_keys || Aring > S.ring_cap) ? 7 : (A > DN_TAB ? 8 : ((mnew0 > min(S.dense_tab, TABMAX) || mnew0 > S.idle_cap) ? 9 :
+        const int why = k > DN_ORDERS ? 4 : (n > DN_CAND ? 5 : (far != 0 ? 6 : ((Aring > S.dense_keys || Aring > S.ring_cap) ? 7 : (A > DN_TAB ? 8 : ((mnew0 > min(tabl, TABMAX) || mnew0 > S.idle_cap) ? 9 :
                         ((PULL && A - Aring > S.dense_keys * 2) ? 10 : 11))))));      // (11: more than DN_TH arrivals)
         atomicAdd(&D.err[why], 1);
     }
@@ -1323,7 +1324,7 @@ __global__ __launch_bounds__(ROWS * LPR, TABMAX > 128 ? DN_MIN_WAVES256 : (LPR =
     const unsigned long long badrows = ballot(bad && lg == 0);
     if (badrows != 0ull && lane == 0) {      // buckets that leave the fast path: vds_read_work; per slot: what the choice of this kernel's form is made from
         atomicAdd(&D.err[2], popc64(badrows));
-        if (D.slow_tick != nullptr) atomicAdd(&D.slow_tick[t], popc64(badrows));
+        if (D.slow_tick != nullptr && t < D.slow_T) atomicAdd(&D.slow_tick[(size_t)t * S.C + c], popc64(badrows));
     }
     if (bad) { rowvalid = false; m = 0; A = 0; Aring = 0; }
     if (!rowvalid) m_raw = 0;
@@ -1346,6 +1347,28 @@ __global__ __launch_bounds__(ROWS * LPR, TABMAX > 128 ? DN_MIN_WAVES256 : (LPR =
         const int l0 = __ffsll((long long)rest) - 1;
         dense_bucket_slow<CT, ST>(*P.Sdev, *P.Ddev, c, rdlane(r, l0), t, reinterpret_cast<const CT *>(blk_g), nc, (DM == 2 || k > 0) ? lds_blk : (const CT *)nullptr);
     }
+}
+
+// One form for the whole launch.  Longest-processing-time-first: all replica chunks of the biggest cluster lead the grid
+// (vds_run launches the tick per replica group: rows [r_lo, r_hi))
+template <bool U8, int DM, int LPR, bool PULL, int TABMAX = DN_TAB, int ROWS = DN_ROWS, bool ST = false>
+__global__ __launch_bounds__(ROWS * LPR, TABMAX > 128 ? DN_MIN_WAVES256 : (LPR == 16 ? DN_MIN_WAVES16 : (LPR == 8 ? DN_MIN_WAVES8 : DN_MIN_WAVES4))) void k_tick_dense(DenseArgs P, int t) {
+    const int nchunks = gridDim.x / P.C;
+    tick_dense_wg<U8, DM, LPR, PULL, TABMAX, ROWS, ST>(P, t, (int)(blockIdx.x / nchunks), P.r_lo + (int)(blockIdx.x % nchunks) * ROWS, P.dense_tab);
+}
+
+// Both forms of one shared day in one launch, chosen per (slot, cluster) (vds_api.hip adapt_dense): every workgroup reads its entry of
+// the slot's block map {cluster in the LPT order, (first row << 1) | form} and runs 32 rows at 8 lanes per replica with 128-entry
+// tables (form 0) or 16 rows at 16 lanes with 256-entry tables (form 1) - 256 threads either way, the LDS carve-up of its form.
+// Scheduled like the 8-lane form (6 wavefronts per SIMD): the 16-lane body has room to spare there (its own kernel runs at 7)
+#ifndef DN_MIN_WAVES_MIX
+#define DN_MIN_WAVES_MIX DN_MIN_WAVES8
+#endif
+template <bool ST>
+__global__ __launch_bounds__(256, DN_MIN_WAVES_MIX) void k_tick_dense_mixed(DenseArgs P, int t) {
+    const int2 e = P.bmap[blockIdx.x];
+    if (e.y & 1) tick_dense_wg<true, 0, 16, true, 256, DN_ROWS, ST>(P, t, e.x, P.r_lo + (e.y >> 1), 256);
+    else tick_dense_wg<true, 0, 8, true, DN_TAB, 32, ST>(P, t, e.x, P.r_lo + (e.y >> 1), P.dense_tab);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1436,7 +1459,7 @@ static void emit_dense_lpr(const Emit &e, const Static &S, const DenseArgs &P, i
 }
 
 // S.self_dev / S.state_dev: device-resident copies of S and D (kept current by vds_api.hip: dev_copy_sync) for the slow path
-void emit_tick_dense(const Emit &e, const Static &S, const State &D, int t, int r_lo, int r_n) {
+static DenseArgs dense_args(const Static &S, const State &D, int r_lo, int r_n) {
     DenseArgs P;
     P.hdr = D.hdr; P.cnt = D.cnt; P.idle = reinterpret_cast<unsigned *>(D.idle); P.ring = reinterpret_cast<uint2 *>(D.ring);
     P.ring_cnt = D.ring_cnt; P.inbox = D.inbox; P.out = D.out; P.err = D.err;
@@ -1449,6 +1472,35 @@ void emit_tick_dense(const Emit &e, const Static &S, const State &D, int t, int 
     P.tdesc = S.tdesc;
     P.stamp = D.stamp; P.dry = D.dry; P.slow_tick = D.slow_tick; P.so_rank = S.so_rank; P.sup = D.sup; P.sup_slot = D.sup_slot;
     P.arr = D.arr; P.so_slot = S.so_slot; P.d_rec = S.d_rec; P.d_first = S.d_first; P.replica_desc2 = S.replica_desc2; P.pull_W = S.pull_W;
+    P.slow_T = D.slow_T; P.bmap = nullptr;
+    return P;
+}
+
+// dynamic LDS of k_tick_dense with `rows` rows of `tab`-entry tables
+static size_t dense_lds(const Static &S, int rows, int tab) {
+    const int bb = (S.max_nc * (S.max_nc + 1) * (S.blk8s ? 1 : 4) + 15) / 16 * 16;
+    // (one order day per replica: the order-record area holds the rows' pickup offsets instead, u16 [16][64] = 2 KB)
+    return (S.n_days > 1 && !S.chunk_days ? DN_ROWS * DN_ORDERS * 2 : DN_ORDERS * 16) + (S.pull ? DN_ORDERS * 8 + DN_CAND * 8 : 0) + (S.dense_st ? DN_ORDERS * 4 : 0) +
+           (size_t)rows * (tab + DN_TPAD) * 4 + bb;
+}
+
+// Forms per (slot, cluster) need one shared day, byte costs, static arrival slots and 32-row workgroups in the 8-lane form
+bool dense_mixed_ok(const Static &S, int slots) {
+    return S.dense && S.n_days <= 1 && S.blk8s != nullptr && S.pull && S.tdesc != nullptr && slots >= 64 && DN_ROWS32;
+}
+
+// Slot t with the forms of its clusters mixed: k_tick_dense_mixed over the whole batch (rows [0, R)), nblk workgroups as the slot's
+// block map bmap lists them.  S: the base (8-lane) form.
+void emit_tick_dense_mixed(const Emit &e, const Static &S, const State &D, int t, const int2 *bmap, int nblk) {
+    DenseArgs P = dense_args(S, D, 0, 0);
+    P.bmap = bmap;
+    const size_t lds = std::max(dense_lds(S, 32, DN_TAB), dense_lds(S, DN_ROWS, 256));
+    if (S.dense_st) emit_dense(e, k_tick_dense_mixed<true>, dim3(nblk), dim3(256), lds, P, t);
+    else emit_dense(e, k_tick_dense_mixed<false>, dim3(nblk), dim3(256), lds, P, t);
+}
+
+void emit_tick_dense(const Emit &e, const Static &S, const State &D, int t, int r_lo, int r_n) {
+    const DenseArgs P = dense_args(S, D, r_lo, r_n);
     const int slots = r_n > 0 ? r_n : (S.rperm != nullptr ? S.rslots : S.R) - r_lo;
     const bool t256 = dense_tab256(S);
     // 32-row workgroups: one shared day, 8 lanes per replica, byte costs, static arrival slots, at least 64 rows in the launch
@@ -1457,10 +1509,7 @@ void emit_tick_dense(const Emit &e, const Static &S, const State &D, int t, int 
     const int rows = rows32 ? 32 : (rows8 ? S.row_gran : DN_ROWS);
     const int rchunks = (slots + rows - 1) / rows;
     const dim3 grid(S.C * rchunks);
-    const int bb = (S.max_nc * (S.max_nc + 1) * (S.blk8s ? 1 : 4) + 15) / 16 * 16;
-    // (one order day per replica: the order-record area holds the rows' pickup offsets instead, u16 [16][64] = 2 KB)
-    const size_t lds = (S.n_days > 1 && !S.chunk_days ? DN_ROWS * DN_ORDERS * 2 : DN_ORDERS * 16) + (S.pull ? DN_ORDERS * 8 + DN_CAND * 8 : 0) + (S.dense_st ? DN_ORDERS * 4 : 0) +
-                       rows * ((t256 ? 256 : DN_TAB) + DN_TPAD) * 4 + bb;
+    const size_t lds = dense_lds(S, rows, t256 ? 256 : DN_TAB);
     if (S.dense_st) {
         // stamp form (neighbour search; vds_api.hip grants it for byte costs, one shared day, static arrival slots)
         if (t256) emit_dense(e, k_tick_dense<true, 0, 16, true, 256, DN_ROWS, true>, grid, dim3(DN_ROWS * 16), lds, P, t);

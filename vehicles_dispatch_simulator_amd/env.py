@@ -270,6 +270,15 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_debug_tick_forms(self._h, _p(out), int(out.size), C.byref(n)))
         return out[:n.value].copy()
 
+    def cluster_forms(self) -> np.ndarray:
+        """Per (slot, cluster) of the day, ``[T, C]``: 1 where ``k_tick_dense`` runs that cluster's buckets in its 16-lane form, 0 in the
+        base form; ``[0, C]`` when the library has made no choice (``vds_debug_cluster_forms``; the choice never changes results).
+        ``cluster_forms().sum()`` counts the (slot, cluster) pairs in the 16-lane form."""
+        out = np.zeros((max(self.T, 1), self.C), dtype=np.uint8)
+        n = C.c_int32()
+        self._chk(self._lib.vds_debug_cluster_forms(self._h, _p(out), C.c_int64(out.size), C.byref(n)))
+        return out[:n.value].copy()
+
     def run_groups(self) -> int:
         """The group count ``run`` uses as the handle stands (1: one launch (pair) per tick over all replicas)."""
         return int(self._lib.vds_get_run_groups(self._h))
