@@ -299,7 +299,9 @@ def test_dense_tick_switches_to_wide_rows_when_the_slow_path_is_crowded(monkeypa
     than 0.1 % of its bucket-ticks to the slow path (here: 200 vehicles parked in one cluster of every replica) the handle takes
     16 lanes per replica and 256-entry tables from the next-but-one episode start on (the counter travels through pinned host
     memory, no synchronisation).  Every episode equals the oracle, before and after the switch; after it the crowded cluster is on
-    the fast path (no slow-path buckets).  VDS_DENSE_ADAPT=0 keeps the first form."""
+    the fast path (no slow-path buckets).  VDS_DENSE_ADAPT=0 keeps the first form.  Settling episodes that stop one slot short of
+    the day leave no per-slot counters: the switch is then the whole day's (no per-slot choice), and the full day after it equals
+    the oracle on the fast path."""
     g = dict(load_golden("tiny_kmeans")); g["V"] = np.int64(200)
     R = 20
     nodes5 = np.flatnonzero(g["node2cluster"] == 5)
@@ -308,7 +310,7 @@ def test_dense_tick_switches_to_wide_rows_when_the_slow_path_is_crowded(monkeypa
     for r in range(R):
         o = Oracle(g["cost"], g["node2cluster"], g["nbr_off"], g["nbr_idx"], 0, False, g["o_release_min"], g["o_pickup"], g["o_delivery"], 200)
         o.reset(init[r]); o.run_day(); exp.append(o.orders())
-    for adapt in ("1", "0"):
+    for adapt, partial in (("1", False), ("0", False), ("1", True)):
         monkeypatch.setenv("VDS_DENSE_ADAPT", adapt)
         env = make_env(g, R, idle_cap=256)
         assert env.main_kernel() == "k_tick_dense"
@@ -316,15 +318,19 @@ def test_dense_tick_switches_to_wide_rows_when_the_slow_path_is_crowded(monkeypa
         slow = []
         for ep in range(5):
             if ep: env.reset_again()
-            env.run(env.T); env.sync()
+            full = not partial or ep == 4
+            env.run(env.T if full else env.T - 1); env.sync()
+            slow.append(env.work()["slow_path_buckets"])
+            if not full:
+                continue
             got = env.orders()
             for r in range(R):
                 for k in ("status", "vehicle", "wait"):
                     np.testing.assert_array_equal(got[k][r], exp[r][k], err_msg="episode %d replica %d %s" % (ep, r, k))
-            slow.append(env.work()["slow_path_buckets"])
         assert slow[0] > 0 and slow[1] == slow[0]
         if adapt == "1": assert slow[-1] == 0 and slow[-2] == 0, slow
         else: assert slow[-1] == slow[0], slow
+        if partial: assert env.tick_forms().size == 0 and env.cluster_forms().shape[0] == 0
         env.close()
 
 

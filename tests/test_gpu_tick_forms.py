@@ -2,8 +2,9 @@
 short, 16 lanes with 256-entry tables where many buckets would leave the fast path.  Results must not depend on it.  In subprocesses
 (the switches are environment variables read when a day is loaded):
   * the two forms alternating slot by slot at 96 replicas (32-row workgroups <-> 16-row workgroups), with and without neighbour search;
-  * the adaptive path itself: a city whose lists outgrow the 128-entry tables in some slots, a low threshold - after three episodes some
-    slots (not all) run the second form, the day graph was rebuilt, and every checked replica still equals the oracle."""
+  * the adaptive path itself, below the 64 replicas that forms per (slot, cluster) need: a city whose lists outgrow the 128-entry tables
+    in some slots, a low threshold - after three episodes some slots (not all) run the second form, the day graph was rebuilt, and every
+    checked replica still equals the oracle."""
 import os
 import subprocess
 import sys
@@ -65,7 +66,8 @@ def test_forms_alternating_slot_by_slot():
     run_worker("alt", [(False, 700, 96, 1, None), (True, 700, 96, 1, None)], VDS_DENSE_TICK_FORMS="alt")
 
 
-def test_per_slot_choice_adapts_and_keeps_results():
-    # (limits chosen so that some slots, fewer than 85 % of them, switch: 114 / 87 of 148; nearly every slot would switch the whole day)
-    out = run_worker("adapt", [(False, 1000, 96, 4, 100), (True, 1000, 96, 4, 120)])
+def test_per_slot_choice_below_64_replicas_adapts_and_keeps_results():
+    # (48 replicas: too few for forms per (slot, cluster), the per-slot rule decides.  Limits chosen so that some slots, fewer than 85 %
+    # of them, switch: 112 / 71 of 148; nearly every slot would switch the whole day)
+    out = run_worker("adapt", [(False, 1000, 48, 4, 50), (True, 1000, 48, 4, 60)])
     assert out.count("ok adapt") == 2
