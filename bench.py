@@ -10,14 +10,18 @@ BASELINE.json configs[1] (192 clusters, 10k vehicles, ~200k orders/day), inputs 
 HBM.  Replicas shard across GPUs with no data-path collective (weak scaling: R per GPU is
 fixed); the only collective is an RCCL all-reduce of the int64[8] aggregate counters per day.
 
-The one JSON line printed by rank 0 also carries
+The one JSON line printed by rank 0 carries the headline (`value`, `ms_per_step`) of the K timed days and what the same run
+read back on the way; a plain run does nothing else.  With --full the line also carries
   roofline      dominant kernel: HBM bytes per launch (rocprofv3 PMC figure of the SAME build, profiles/traffic.json; else
                 the bytes the data layout has to move, and the line says which) / average launch duration (one HIP event
                 pair on the kernel's stream around a whole day / launches) vs 8 TB/s HBM; next to it SURVEY.md 8(d)'s
                 accounting bytes and the limiter the counters name;
   cpu_baseline  the CPU oracle (a C port of the reference algorithm, 1 thread) timed on this
                 host on a bounded sample of the same workload;
-  cpu_baseline_all_cores  the same oracle as one independent single-replica process per host core.
+  cpu_baseline_all_cores  the same oracle as one independent single-replica process per host core;
+and the side legs (per-replica order days, neighbour search, stress, hooked slot, episode reset / turnover, fallbacks), each
+with its own handle or days outside the timed region; under torch.distributed.run the all-reduce by itself (collective.allreduce_us).
+The --no-* options below switch single legs of a --full run off.
 """
 from __future__ import annotations
 
@@ -188,6 +192,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--replicas", type=int, default=1024, help="replicas PER GPU")
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg4", "cfg5"])
+    ap.add_argument("--full", action="store_true", help="also run everything besides the headline: roofline passes, CPU baselines, side legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-neighbour-leg", action="store_true", help="skip the extra configs[3] (neighbour search) leg")
     ap.add_argument("--check", action="store_true", help="verify replica 0 against the oracle after the run")
@@ -202,8 +207,9 @@ def main():
     if a.steps < 1:
         ap.error("--steps must be at least 1")
     marks = [("start", time.perf_counter())]          # wall clock of the legs (leg_seconds in the line)
-    def mark(name):
-        marks.append((name, time.perf_counter()))
+    def mark(name, ran=True):
+        if ran:
+            marks.append((name, time.perf_counter()))
 
     import torch
     from vehicles_dispatch_simulator_amd import dist as vdist
@@ -286,36 +292,38 @@ def main():
     per_rank = None
     if dist is not None:
         # what the first real N > 1 run needs to explain itself: every rank's own wall time, its first GLOBAL replica and that
-        # replica's start-node seed (+ a fingerprint of the nodes it drew), and the collective by itself
+        # replica's start-node seed (+ a fingerprint of the nodes it drew), and (--full) the collective by itself
         import zlib
         mine_t = torch.tensor([elapsed / a.steps * 1e3, float(first), float(w.veh_seed + first), float(zlib.crc32(np.ascontiguousarray(init[0]).tobytes()))],
                               dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         allt = [torch.zeros_like(mine_t) for _ in range(world)]
         dist.all_gather(allt, mine_t)
         allt = torch.stack(allt).cpu().numpy()
-        ar_n = 20
-        if backend == "nccl":
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            probe = totals.clone()
-            vdist.allreduce_counters(probe); torch.cuda.synchronize()
-            e0.record(stream)
-            for _ in range(ar_n):
-                vdist.allreduce_counters(probe)
-            e1.record(stream); e1.synchronize()
-            ar_us = e0.elapsed_time(e1) / ar_n * 1e3
-            ar_how = "HIP events on the bench stream around %d back-to-back RCCL all-reduces of int64[8]" % ar_n
-        else:
-            probe = totals.cpu()
-            vdist.allreduce_counters(probe)
-            tq = time.perf_counter()
-            for _ in range(ar_n):
-                vdist.allreduce_counters(probe)
-            ar_us = (time.perf_counter() - tq) / ar_n * 1e6
-            ar_how = "host clock around %d back-to-back gloo all-reduces of int64[8] (host memory)" % ar_n
-        vdist.ALLREDUCE_CALLS -= ar_n + 1      # (the probe is not part of the job's count)
         per_rank = {"ms_per_step": [float(x) for x in allt[:, 0]], "ms_per_step_min": float(allt[:, 0].min()), "ms_per_step_max": float(allt[:, 0].max()),
                     "first_replica": [int(x) for x in allt[:, 1]], "first_replica_seed": [int(x) for x in allt[:, 2]],
-                    "first_replica_nodes_crc32": [int(x) for x in allt[:, 3]], "allreduce_us": ar_us, "allreduce_timing": ar_how}
+                    "first_replica_nodes_crc32": [int(x) for x in allt[:, 3]]}
+        if a.full:
+            ar_n = 20
+            if backend == "nccl":
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                probe = totals.clone()
+                vdist.allreduce_counters(probe); torch.cuda.synchronize()
+                e0.record(stream)
+                for _ in range(ar_n):
+                    vdist.allreduce_counters(probe)
+                e1.record(stream); e1.synchronize()
+                ar_us = e0.elapsed_time(e1) / ar_n * 1e3
+                ar_how = "HIP events on the bench stream around %d back-to-back RCCL all-reduces of int64[8]" % ar_n
+            else:
+                probe = totals.cpu()
+                vdist.allreduce_counters(probe)
+                tq = time.perf_counter()
+                for _ in range(ar_n):
+                    vdist.allreduce_counters(probe)
+                ar_us = (time.perf_counter() - tq) / ar_n * 1e6
+                ar_how = "host clock around %d back-to-back gloo all-reduces of int64[8] (host memory)" % ar_n
+            vdist.ALLREDUCE_CALLS -= ar_n + 1      # (the probe is not part of the job's count)
+            per_rank.update(allreduce_us=ar_us, allreduce_timing=ar_how)
         elapsed = vdist.max_over_ranks(elapsed, device="cuda")
     agg = totals.cpu().numpy()
     mark("import, workload, handle, warm-up, timed days")
@@ -324,13 +332,15 @@ def main():
         dumped = dump_outputs(a.dump_outputs, env, agg, first)
         mark("dump_outputs")
 
+    # Everything from here to the --check pass runs with --full only: a plain run goes from its timed days (and --dump-outputs)
+    # straight to the line.
     # ---- roofline pass (rank 0): per-launch duration of the dominant kernel, HIP events on its stream.  The day is
     #      stepped slot by slot so that the packed observations (device tensors) give the exact number of idle-list
     #      entries the kernel loaded: sum of PerMatchIdleVehicles over the (replica, cluster) buckets that had orders.
     roofline = None
     work = env.work()         # work of the last day on this rank
     build_id = (env._lib.vds_build_id() or b"").decode()
-    if rank == 0:
+    if rank == 0 and a.full:
         env.reset_again()
         env.profile(True)
         env.run(T)                                 # per-launch pass: HIP event pairs around every launch of the dominant kernel
@@ -432,9 +442,9 @@ def main():
     # ---- per-replica order days (rank 0, N = 1): the headline replays ONE day in every replica, which lets 16 replicas
     #      share staged order records and keeps per-order control flow wave-uniform.  The same workload with D distinct
     #      days (replica r replays day r % D; vds_load_order_days, k_tick_rows' per-row variant) is timed next to it.
-    mark("roofline passes")
+    mark("roofline passes", a.full)
     per_days = None
-    if rank == 0 and world == 1 and a.distinct_days > 1 and a.workload != "cfg5":
+    if a.full and rank == 0 and world == 1 and a.distinct_days > 1 and a.workload != "cfg5":
         days = workloads.distinct_days(w, a.distinct_days)
         per_days = {"distinct_days": a.distinct_days, "unit": "env-steps*replicas/s",
                     "note": "same city / vehicles / order count; interleaved: replica r replays day r %% %d (the library STORES the replicas "
@@ -484,9 +494,9 @@ def main():
 
     # ---- neighbour-search mode (rank 0, N = 1, only next to the headline workload): BASELINE configs[3] - the same city with
     #      NeighborCanServer and a 2000 m service radius (DFS depth 2) - a few days, so that the line also shows the second tick path
-    mark("per_replica_days")
+    mark("per_replica_days", a.full)
     nbr = None
-    if rank == 0 and world == 1 and a.workload == "cfg2" and not a.no_neighbour_leg:
+    if a.full and rank == 0 and world == 1 and a.workload == "cfg2" and not a.no_neighbour_leg:
         w4 = workloads.didi_day("cfg4", neighbor=True, service_m=2000.0)
         env4 = w4.make_env(R, device=local_rank, stream=stream.cuda_stream)
         env4.reset(w4.vehicle_nodes(R))
@@ -511,9 +521,9 @@ def main():
 
     # ---- configs[4] (rank 0, N = 1, next to the headline): the stress city - 2048 clusters, 16384 nodes, 100k vehicles, 2M orders per replica
     #      and day - at 128 replicas on one GPU, three days
-    mark("neighbour_search")
+    mark("neighbour_search", a.full)
     stress = None
-    if rank == 0 and world == 1 and a.workload == "cfg2" and a.stress:
+    if a.full and rank == 0 and world == 1 and a.workload == "cfg2" and a.stress:
         try:
             w5 = workloads.stress()
             R5 = 128
@@ -546,9 +556,9 @@ def main():
     #      observations, policy and actions on the device: step -> obs_torch -> a small torch policy -> apply_dispatch_torch (K = 8
     #      moves per city and slot) -> advance.  Timed next to the same loop without the hook (step -> advance) and the hook-less
     #      vds_run above.
-    mark("stress")
+    mark("stress", a.full)
     hooked = None
-    if rank == 0 and world == 1 and a.hooked and a.workload == "cfg2":
+    if a.full and rank == 0 and world == 1 and a.hooked and a.workload == "cfg2":
         K = 8
         n2c = np.asarray(w.city.node2cluster)
         some_node_of = torch.tensor([int(np.flatnonzero(n2c == c)[0]) if (n2c == c).any() else 0 for c in range(env.C)], dtype=torch.int32, device="cuda")
@@ -726,9 +736,9 @@ def main():
     # ---- the episode reset three ways (rank 0, N = 1): start nodes resident (vds_reset_again: what the timed steps use), drawn on
     #      the device per episode (vds_reset_random: one random.Random(seed) stream per replica, the reference's InitVehiclesIntoCluster
     #      draws bit for bit), generated on the host and uploaded (vds_reset: what an RL loop with fresh start nodes paid before)
-    mark("hooked_slot")
+    mark("hooked_slot", a.full)
     episode_reset = None
-    if rank == 0 and world == 1 and a.hooked and a.workload in ("cfg2", "cfg5"):
+    if a.full and rank == 0 and world == 1 and a.hooked and a.workload in ("cfg2", "cfg5"):
         try:
             def tm(f, n):
                 f(); env.sync()
@@ -750,9 +760,9 @@ def main():
 
     # ---- the documented fallbacks (rank 0, N = 1): every tick path a configuration can end up on has a number next to the default's
     #      (DESIGN.md 5).  A few days each; the serial reference form of the neighbour search on 128 replicas (it takes seconds per day)
-    mark("episode_reset")
+    mark("episode_reset", a.full)
     fallbacks = None
-    if rank == 0 and world == 1 and a.fallbacks and a.workload == "cfg2":
+    if a.full and rank == 0 and world == 1 and a.fallbacks and a.workload == "cfg2":
         fallbacks = {"unit": "env-steps*replicas/s", "note": "same workload and replica count as the headline unless said; vds_config.force_generic selects the path"}
         def leg(wl, Rl, fg, nd, environ=None):
             saved = {k: os.environ.get(k) for k in (environ or {})}
@@ -789,9 +799,9 @@ def main():
     #      simulator.py:130-212).  (a) another replica -> day map over resident days (vds_set_replica_days: nothing rebuilt),
     #      (b) a new day on a loaded handle (vds_load_orders: host tables by counting sorts, the neighbour search's visit rows built
     #      on the device), (c) 16 new days (vds_load_order_days: the days built by worker threads)
-    mark("fallbacks")
+    mark("fallbacks", a.full)
     episode_turnover = None
-    if rank == 0 and world == 1 and a.hooked and a.workload in ("cfg2", "cfg4"):
+    if a.full and rank == 0 and world == 1 and a.hooked and a.workload in ("cfg2", "cfg4"):
         try:
             def wall(f, n):
                 f(); torch.cuda.synchronize()
@@ -821,7 +831,7 @@ def main():
         finally:
             env.reset(init)
 
-    mark("episode_turnover")
+    mark("episode_turnover", a.full)
     check = None
     if a.check and rank == 0:
         from oracle.oracle import Oracle
@@ -839,11 +849,11 @@ def main():
         check = bool(ok)
 
     cpu = cpu_all = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(w, init[: min(R, 16)])
         cpu_all = cpu_baseline_all_cores(w, init[: min(R, 64)])
 
-    mark("check, cpu_baseline")
+    mark("check, cpu_baseline" if a.full else "check", a.full or a.check)
     if rank == 0:
         env_steps = T * R * world * a.steps
         out = {
@@ -858,12 +868,15 @@ def main():
                        "parallelism": "replica-sharded x%d, RCCL all-reduce of int64[8] metrics per day" % world},
             "match_evals_per_s": float(work["evals"]) * world * a.steps / elapsed if work["evals"] else None,
             "slow_path_buckets_last_day": int(work.get("slow_path_buckets", 0)),      # buckets the fast kernel handed to a slower path (rank 0)
-            "roofline": roofline, "cpu_baseline": cpu, "build": build_id,
+            "roofline": roofline, "cpu_baseline": cpu, "build": build_id, "full": a.full,
         }
+        if not a.full:                # (a plain run measures neither)
+            del out["roofline"], out["cpu_baseline"]
         if dist is not None:
             out["collective"] = {"backend": dist.get_backend(), "world_size": world, "allreduce_calls": vdist.ALLREDUCE_CALLS,
-                                 "payload": "int64[8] aggregate counters per day",
-                                 "allreduce_us": per_rank["allreduce_us"], "allreduce_timing": per_rank["allreduce_timing"]}
+                                 "payload": "int64[8] aggregate counters per day"}
+            if a.full:
+                out["collective"].update(allreduce_us=per_rank["allreduce_us"], allreduce_timing=per_rank["allreduce_timing"])
             out["per_rank"] = {k: v for k, v in per_rank.items() if not k.startswith("allreduce")}
         if cpu_all is not None:
             out["cpu_baseline_all_cores"] = cpu_all

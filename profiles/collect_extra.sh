@@ -6,7 +6,7 @@ export VDS_RUN_GROUPS=1      # one launch per tick over all replicas: per-launch
 TAG=$1; shift
 O=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-neighbour-leg --distinct-days 0 $@"
+B="python bench.py --full --no-cpu-baseline --no-neighbour-leg --distinct-days 0 $@"
 rocprofv3 -L > $O/counters_list.txt 2>&1
 timeout 300 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum --kernel-trace --output-format csv -d $O/ea -- $B --steps 1 --warmup 0 > $O/ea.log 2>&1
 timeout 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_ATOMIC_sum --kernel-trace --output-format csv -d $O/tcc -- $B --steps 1 --warmup 0 > $O/tcc.log 2>&1

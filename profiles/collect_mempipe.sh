@@ -6,7 +6,7 @@
 export TMPDIR=/tmp
 OUT=$1; shift
 O=/tmp/mempipe; rm -rf $O; mkdir -p $O
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-neighbour-leg --distinct-days 0 $@ --steps 1 --warmup 0"
+B="python $(cd "$(dirname "$0")/.." && pwd)/bench.py --full --no-cpu-baseline --no-neighbour-leg --distinct-days 0 $@ --steps 1 --warmup 0"
 i=0
 for grp in "TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TA_TOTAL_WAVEFRONTS_sum" \
            "TCP_PENDING_STALL_CYCLES_sum TCP_TCR_TCP_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_GATE_EN1_sum" \

@@ -61,7 +61,7 @@ def test_bench_py_itself_with_two_ranks():
     2 R replicas."""
     Rr = 24
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--replicas", str(Rr), "--no-cpu-baseline", "--no-neighbour-leg", "--distinct-days", "0", "--no-hooked-leg", "--no-distinct-all"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", VDS_BENCH_BACKEND="gloo")
     res = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
