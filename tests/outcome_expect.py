@@ -1,4 +1,5 @@
-"""Expected per-cluster order outcomes of every slot (``vds_outcomes_device``), built with numpy from a golden fixture alone.
+"""Expected per-cluster order outcomes of every slot (``vds_outcomes_device``), built with numpy from a golden fixture alone
+(``expected_outcomes``), or from the CPU oracle's statuses before and after each slot (``processed_planes``: any release order).
 
 The goldens were captured from the unmodified reference, so the expectation does not rest on this engine.  In the reference an
 order is processed by ``MatchFunction`` in the first slot whose window ``ReleasTime < RealExpTime + TimePeriods`` admits it
@@ -35,6 +36,25 @@ def expected_outcomes(release_min, pickup, node2cluster, status, wait, value, ti
     np.add.at(out[:, :, REJECTED], (slot[r], cl[r]), 1)
     np.add.at(out[:, :, WAIT_SUM], (slot[s], cl[s]), np.asarray(wait, dtype=np.int64)[s])
     np.add.at(out[:, :, VALUE_SUM], (slot[s], cl[s]), np.asarray(value, dtype=np.int64)[s])
+    return out
+
+
+def processed_planes(before, after, pickup_cluster, wait, value, C):
+    """int64 ``[C, 4]`` of one slot from the CPU oracle's own stepping: the orders whose status turned non-zero between ``before`` (the
+    statuses read before the slot's ``begin_tick``) and ``after`` (read after it), by pickup cluster.  ``wait`` / ``value``: the oracle's
+    ``PickupWaitTime`` / ``OrderValue``.  Unlike ``order_slots`` it assumes nothing about the order of the releases, and the order that is
+    never processed (status 0) is in no slot."""
+    before, after = np.asarray(before), np.asarray(after)
+    cl = np.asarray(pickup_cluster, dtype=np.int64)
+    new = (before == 0) & (after != 0)
+    assert (cl[new] >= 0).all()
+    out = np.zeros((int(C), 4), dtype=np.int64)
+    s = new & (after == 1)
+    r = new & (after == 2)
+    np.add.at(out[:, SERVED], cl[s], 1)
+    np.add.at(out[:, REJECTED], cl[r], 1)
+    np.add.at(out[:, WAIT_SUM], cl[s], np.asarray(wait, dtype=np.int64)[s])
+    np.add.at(out[:, VALUE_SUM], cl[s], np.asarray(value, dtype=np.int64)[s])
     return out
 
 

@@ -381,3 +381,98 @@ def test_batched_hooks_policy_over_all_replicas_matches_oracle_replay():
     assert idle_total + fly_total == len(sim.Vehicles)
     assert int((sim.last_rejects.cpu().numpy() == cn[:, 1]).sum()) >= 1     # (counters of the last slot, read inside the hook)
     sim.env.close()
+
+
+class CountingPolicySim(GraphPolicySim):
+    """GraphPolicySim that counts the calls of ``BatchedPolicy`` made under graph capture."""
+
+    def BatchedPolicy(self, ob):
+        import torch
+        self.captures += int(torch.cuda.is_current_stream_capturing())
+        return GraphPolicySim.BatchedPolicy(self, ob)
+
+
+@pytest.mark.parametrize("outcomes", [False, True], ids=["no-outcomes", "outcomes"])
+def test_reload_recaptures_the_batched_policy(tmp_path, outcomes):
+    """``Reload`` to a day whose tables make the library re-make the handle's state tables (a longer and denser day: more slots, longer
+    arrival rings): the policy captured on the first day read the old observation (and outcome) blocks.  After the Reload it is captured
+    again, reads the live blocks, and both days equal the CPU oracle replaying the actions the policy logged on the device."""
+    import os, shutil, time
+    import torch
+    from oracle.oracle import Oracle
+    from oracle.ref_harness import write_reference_data_dir
+    from test_world_loader import rebuild_inputs
+    from vehicles_dispatch_simulator_amd import synth
+    from vehicles_dispatch_simulator_amd.env import neighbors_to_csr
+    os.environ["TZ"] = "UTC"; time.tzset()
+    g = load_golden("tiny_focus_grid")
+    city, start, pick, dele = rebuild_inputs(g)
+    short = start < start[0] + 2 * 3600                           # day 1: the first two hours of the fixture's day
+    write_reference_data_dir(str(tmp_path), city, start[short], pick[short], dele[short], n_drivers=int(g["V"]), cluster_mode="Grid")
+    data = os.path.join(str(tmp_path), "data")
+    start2, pick2, dele2 = synth.make_orders(91, city.N, 6 * start.size)     # day 2: a whole day, six times the orders
+    write_reference_data_dir(os.path.join(str(tmp_path), "day2"), city, start2, pick2, dele2, n_drivers=int(g["V"]), cluster_mode="Grid", date="1102")
+    os.makedirs(os.path.join(data, "test"))
+    shutil.copy(os.path.join(str(tmp_path), "day2", "data", "order_20161102.csv"), os.path.join(data, "test", "order_20161102.csv"))
+    R = 16
+    sim = CountingPolicySim(ClusterMode="Grid", DemandPredictionMode="None", DispatchMode="Simulation", VehiclesNumber=int(g["V"]),
+                            TimePeriods=TIMESTEP, LocalRegionBound=tuple(g["focus_bound"].tolist()), SideLengthMeter=float(g["side_m"]),
+                            VehiclesServiceMeter=float(g["service_m"]), NeighborCanServer=True, FocusOnLocalRegion=True, DataDir=data, Quiet=True,
+                            Replicas=R, VehicleSeed=613, BatchedHooks=True, BatchedOutcomes=outcomes)
+    random.seed(int(g["seed"]))
+    sim.CreateAllInstantiate("1101")
+    n2c = sim._world.node2cluster
+    C = len(sim.Clusters)
+    sim.first_node = torch.tensor([int(np.flatnonzero(n2c == c)[0]) if (n2c == c).any() else 0 for c in range(C)], device="cuda")
+    sim.captures, sim.begin_calls = 0, 0
+    sim.slot = torch.zeros(1, dtype=torch.int64, device="cuda")
+    sim.log = torch.full((400, R, 2, 3), -1, dtype=torch.int32, device="cuda")
+    Ts = []
+    for day in (1, 2):
+        if day == 2:
+            sim.Reload("1102")
+        T = sim.env.T
+        Ts.append(T)
+        init = sim._init_nodes.copy()
+        sim.SimCity()
+        assert sim.BatchedPolicyGraphError is None, sim.BatchedPolicyGraphError
+        assert sim.step == T and int(sim.slot.item()) == T and sim.begin_calls == day
+        assert sim.captures == day, "day %d: the policy was captured %d times" % (day, sim.captures)
+        st = sim._bp_state
+        assert st is not None and st["graph"] is not None
+        planes = ("idle_pre", "idle_now", "supply", "cl_orders", "inflight")
+        base = sim.env.obs_device_ptr()
+        for k in sim.BatchedPolicyPlanes:
+            assert st["obs"][k].data_ptr() == base + 4 * planes.index(k) * R * C, (day, k)
+        if outcomes:
+            oc = sim.env.outcomes_device_ptr()
+            for i, k in enumerate(("served", "rejected", "wait_sum", "value_sum")):
+                assert st["obs"][k].data_ptr() == oc + 8 * i * R * C, (day, k)
+        # every replica against the oracle replaying the logged actions
+        W = sim._world
+        off, idx = neighbors_to_csr(W.neighbors)
+        log = sim.log.cpu().numpy()
+        got, cn = sim.env.orders(), sim.env.counters()
+        n_dispatched = 0
+        for r in range(R):
+            o = Oracle(W.cost, W.node2cluster, off, idx, W.depth_limit, True, W.o_release_min, W.o_pickup, W.o_delivery, len(sim.Vehicles))
+            o.reset(init[r])
+            assert o.num_ticks == T
+            for t in range(T):
+                o.begin_tick()
+                L = o.lists()
+                vehs, tgts = [], []
+                for cl, pos, tg in log[t, r]:
+                    if cl >= 0:
+                        vehs.append(int(L["idle_veh"][L["idle_off"][cl] + pos])); tgts.append(int(tg))
+                if vehs:
+                    o.dispatch(np.array(vehs), np.array(tgts))
+                    n_dispatched += len(vehs)
+                o.end_tick()
+            exp, oc_ = o.orders(), o.counters()
+            for k in ("status", "vehicle", "wait"):
+                np.testing.assert_array_equal(got[k][r][:exp[k].size], exp[k], err_msg="day %d replica %d %s" % (day, r, k))
+            assert (cn[r, 0], cn[r, 1], cn[r, 3], cn[r, 4], cn[r, 5], cn[r, 7]) == (oc_["order_num"], oc_["reject_num"], oc_["wait_sum"], oc_["dispatch_num"], oc_["dispatch_cost"], oc_["evals"]), (day, r)
+        assert n_dispatched > 0
+    assert Ts[1] > Ts[0]
+    sim.env.close()

@@ -270,6 +270,10 @@ class Simulation(object):
                                           tick_minutes=self._tick_minutes, reject_threshold=PICKUP_REJECT_THRESHOLD,
                                           device=self.Device, **self._device_kwargs)
             self._env_world = W
+        # the load may re-make the handle's state tables (the observation and outcome blocks among them) at addresses the allocator may
+        # hand back unchanged: the captured policy and the day graph that embeds it are dropped, the next policy day captures again
+        self._bp_state = None
+        self.env.run_hooked_invalidate()
         self.env.load_orders(rel, W.o_pickup, W.o_delivery)
 
     def Reload(self, OrderFileDate="1101"):
@@ -633,8 +637,8 @@ class Simulation(object):
         captured (the reason is kept in ``self.BatchedPolicyGraphError``; the caller then runs slot by slot)."""
         import torch
         st = getattr(self, "_bp_state", None)
-        # (keyed by the outcome block's address too: a Reload that re-makes the state tables moves it, and a captured policy must not
-        # go on reading the freed block)
+        # (dropped by every load of orders - _build_orders_and_env; keyed by the outcome block's address too, which the outcome switch
+        # of the same handle changes)
         outc = self._outcome_block_ptr()
         if st is not None and st["env"] is self.env and st.get("outc") == outc:
             return st if st["graph"] is not None else None        # (a capture that failed on this handle is not tried again)
