@@ -54,6 +54,13 @@ int vds_debug_tick_forms(vds_handle *h, uint8_t *out, int32_t cap, int32_t *n_ou
  * *n_out = T (0: no choice was made). */
 int vds_debug_cluster_forms(vds_handle *h, uint8_t *out, int64_t cap, int32_t *n_out);
 
+/* the layout decision as the handle stands (tests/test_gpu_thresholds.py), cap >= 10 words: out[0] dense layout (k_tick_dense),
+ * [1] its stamp form (neighbour search on the dense layout), [2] cost blocks of the dense layout: 1 bytes, 0 ints, [3] u8_ok (every cost
+ * of the matrix in 0..255), [4] the byte copy of the whole matrix exists, [5] fast_ok (packed keys), [6] window_live, [7] seq_pad, [8]
+ * lanes per replica of k_tick_dense, [9] its fast-path table size (128 / 256); -1 where a value does not apply (no orders loaded, no
+ * dense layout, no neighbour search); words past 10 are -1. */
+int vds_debug_layout(vds_handle *h, int32_t *out, int32_t cap);
+
 /* DPP primitives of the kernels on nwaves x 64 int32 values (tests/test_gpu_primitives.py): out_wave [nwaves] wavefront
  * minima; out_rowmin / out_rowsum / out_rowscan [nwaves * 64] per-lane 16-lane-row minimum, row sum and inclusive row scan */
 int vds_selftest_dpp(vds_handle *h, const int32_t *in, int32_t *out_wave, int32_t *out_rowmin, int32_t *out_rowsum,

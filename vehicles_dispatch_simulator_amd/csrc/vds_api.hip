@@ -418,6 +418,27 @@ extern "C" int vds_debug_cluster_forms(vds_handle *h, uint8_t *out, int64_t cap,
     *n_out = T;
     return VDS_OK;
 }
+// the layout decision as the handle stands (include/vds_debug.h: word order, -1 = does not apply)
+extern "C" int vds_debug_layout(vds_handle *h, int32_t *out, int32_t cap) {
+    if (!h || !out || cap < 10) return VDS_EINVAL;
+    const Static &S = h->S;
+    const bool st = h->have_static, ord = h->have_orders;
+    const int32_t w[10] = {
+        ord ? S.dense : -1,
+        ord ? S.dense_st : -1,
+        !st ? -1 : S.blk8s ? 1 : S.blk32s ? 0 : -1,
+        st ? S.u8_ok : -1,
+        st ? (S.cost8 != nullptr) : -1,
+        st ? S.fast_ok : -1,
+        st ? S.window_live : -1,
+        st && h->dfs_mode ? S.seq_pad : -1,
+        ord && S.dense ? S.dense_lpr : -1,
+        ord && S.dense ? S.dense_tab : -1,
+    };
+    std::copy(w, w + 10, out);
+    for (int i = 10; i < cap; ++i) out[i] = -1;
+    return VDS_OK;
+}
 extern "C" int vds_debug_graph_pool_size() {      // executable graphs kept alive past their handle's use (tests): none any more
     return 0;
 }

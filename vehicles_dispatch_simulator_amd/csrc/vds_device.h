@@ -35,8 +35,10 @@ enum {
                         // Every other writer of a header leaves 0 here ("the list is compact") and needs to know nothing about it
     // words 8 .. 13: 32-bit partial counters (CNT_ORDERS .. CNT_ARRIVALS) of the dense tick's byte-cost fast path (round 5): the bucket's
     // header and its counters are ONE 64-byte record - one read request and one write request per bucket and tick instead of two
-    // each (header 32 B + counters 64 B).  Per tick a bucket adds at most 64 orders x 256 candidates / 254 minutes, a day has at most
-    // 65 535 slots: the sums stay below 2^31.  Every other path adds to the 64-bit table `cnt`; k_reduce_counters sums both.
+    // each (header 32 B + counters 64 B).  Only the byte-block layout uses them, and byte blocks exist only while every cost of the WHOLE
+    // matrix is <= 255 (Static.u8_ok, vds_api.hip load_static) - so an order's wait AND its OrderValue (a cost between its pickup and its
+    // delivery, which may lie in another cluster) are <= 255.  Per tick a bucket adds at most 64 orders x 256 candidates / 255 minutes, a
+    // day has at most 65 535 slots: the sums stay below 2^31.  Every other path adds to the 64-bit table `cnt`; k_reduce_counters sums both.
     HDR_CNT32 = 8,
     HDR_WORDS = 16
 };

@@ -1154,9 +1154,10 @@ __global__ __launch_bounds__(64) void k_dispatch(Static S, State D, int t, int n
                 atomicOr(&D.err[0], ERR_DISPATCH);
             }
         }
-        if (!counted) cst = 0;
-        for (int o = 32; o > 0; o >>= 1) cst += __shfl_xor(cst, o, WAVE);
-        cost_sum += cst;
+        // (64-bit sum: the generic layout takes any int32 cost, and 64 of them can pass 2^31)
+        long long cs = counted ? (long long)cst : 0ll;
+        for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o, WAVE);
+        cost_sum += cs;
         ndone += popc64(ballot(ok));
         ncount += popc64(ballot(counted));
     }
@@ -1387,7 +1388,7 @@ __global__ __launch_bounds__(64) void k_dispatch_dense(Static S, State D, int t,
             const size_t b = (size_t)c * S.R + r;
             const IdleRef idle = idle_ref(S, D, c, r);
             const bool mine = (grp >> lane) & 1ull;
-            int csum = (mine && ok) ? cst : 0;
+            long long csum = (mine && ok) ? (long long)cst : 0ll;      // (64-bit: any int32 cost on the generic layout)
             for (int o = 32; o > 0; o >>= 1) csum += __shfl_xor(csum, o, WAVE);
             const unsigned long long okg = ballot(mine && ok);
             const int ndone = popc64(okg);

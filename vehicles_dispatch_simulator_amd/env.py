@@ -279,6 +279,15 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_debug_cluster_forms(self._h, _p(out), C.c_int64(out.size), C.byref(n)))
         return out[:n.value].copy()
 
+    def layout(self) -> Dict[str, int]:
+        """The host's layout decision as the handle stands (``vds_debug_layout``; -1 where a value does not apply): ``dense``
+        (``k_tick_dense``), ``dense_st`` (its stamp form: neighbour search on the dense layout), ``blk8`` (1 byte cost blocks, 0 int
+        blocks), ``u8_ok``, ``cost8``, ``fast_ok``, ``window_live``, ``seq_pad``, ``dense_lpr``, ``dense_tab``."""
+        out = np.full(10, -1, dtype=np.int32)
+        self._chk(self._lib.vds_debug_layout(self._h, _p(out), int(out.size)))
+        return dict(zip(("dense", "dense_st", "blk8", "u8_ok", "cost8", "fast_ok", "window_live", "seq_pad", "dense_lpr", "dense_tab"),
+                        out.tolist()))
+
     def run_groups(self) -> int:
         """The group count ``run`` uses as the handle stands (1: one launch (pair) per tick over all replicas)."""
         return int(self._lib.vds_get_run_groups(self._h))
