@@ -223,8 +223,8 @@ int vds_run(vds_handle *h, int32_t n_ticks);
  * applied as it stands) -> vds_apply_dispatch_device(K, dev_actions), the DispatchFunction body (:1083; K = 0: none) ->
  * vds_advance (:1090-1091).  The whole run is ONE executable graph (built on first use, replayed while nothing it was built for
  * has changed; the policy is embedded as a child graph - it is copied: re-capture it and pass the new handle to change it): one
- * submission per call instead of three or four launches per slot.  The replicas run as the groups of vds_run in parallel branches
- * (the observation and dispatch kernels of one group under the tick of another); the policy node joins them once per slot.
+ * submission per call instead of three or four launches per slot.  The graph is one chain of nodes; replica groups (only when
+ * vds_set_run_groups asked for them) are launches of that chain, the policy node behind the last group's planes.
  * Results are those of the stepwise loop.  Asynchronous on the handle's stream, which must be the stream the policy was
  * captured on, or ordered with it.  Errors of skipped actions surface at the next vds_sync as for vds_apply_dispatch_device.
  * `planes`: bits 0-4 the observation planes of vds_obs_device_planes; bit 5 (VDS_PLANE_OUTCOMES) adds the slot's per-cluster order
@@ -240,19 +240,13 @@ int vds_run_hooked(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, co
  * vds_run_hooked embeds the policy again. */
 int vds_run_hooked_invalidate(vds_handle *h);
 
-/* Scheduling of vds_run (no reference counterpart, results do not depend on it): the replicas run as `groups` independent
- * groups (replicas never interact inside :1048-1091 without hooks) - in neighbour-search mode (hybrid tick) the stamp-mode
- * k_tick_rows of one group under the k_dfs_walk of the others, without neighbour search two chains of half-size k_tick_dense
- * (k_tick_rows) launches whose kernel boundaries overlap.  Defaults: plain tick 2 groups from 256 replicas on (large cities: from clusters x replicas >= 192 x 256
- * and 32 replicas on), hybrid tick 2 from 512 and 3 from 1024 replicas on.  stagger 2: the groups' k_tick_rows launches are
- * serialised round-robin by extra graph edges (keeps the groups out of phase), 1: first tick only, 0: free-running.
- * groups <= 0 / stagger < 0: library default (environment VDS_RUN_GROUPS / VDS_RUN_STAGGER).  1 <= groups <= 16.
- * The groups are parallel branches of the hipGraph vds_run replays (runs of >= 8 slots); eager runs (VDS_RUN_GRAPH=0, short
- * runs, profiling) keep one launch pair per tick over all replicas.  An executable graph with parallel branches is never
- * destroyed while the process lives (its destruction races with the HIP runtime's completion handler): a handle that lets go of
- * one parks it in a process-wide pool, the next handle that needs that shape re-targets it in place (hipGraphExecUpdate).  No
- * vds_* call synchronises the device or sleeps; what stays allocated is host memory of one graph per shape and per handle that
- * held one at the same time. */
+/* Scheduling of vds_run and vds_run_hooked (no reference counterpart, results do not depend on it): the replicas run as `groups`
+ * groups with launches of their own (replicas never interact inside :1048-1091; boundaries at multiples of 16 replicas).  The
+ * groups are launches of the hipGraph that vds_run replays (runs of >= 8 slots), one after another: the day graph is ONE chain
+ * of nodes, parallel branches are not used (executable graphs that had them crashed the HIP runtime when they were destroyed), so
+ * more than one group only adds launches and the default is one.  Eager runs (VDS_RUN_GRAPH=0, short runs, profiling) keep one
+ * launch (pair) per tick over all replicas.  groups <= 0: library default (environment VDS_RUN_GROUPS, else 1).  1 <= groups <= 16.
+ * stagger (0 / 1 / 2, negative: default) ordered the groups while they were parallel branches: it is accepted and has no effect. */
 int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger);
 /* The group count vds_run uses as the handle stands (1: one launch (pair) per tick over all replicas). */
 int vds_get_run_groups(vds_handle *h);

@@ -3,6 +3,7 @@
 #include "../../include/vds.h"
 #include "../../include/vds_debug.h"
 #include "vds_device.h"
+#include "vds_launch.h"
 
 #include <algorithm>
 #include <unordered_map>
@@ -23,48 +24,6 @@
 #include <execinfo.h>
 #include <signal.h>
 #include <unistd.h>
-
-namespace vds {
-void launch_reset(const Static &, const State &, const int *, hipStream_t);
-bool reset_uses_image(const Static &);
-void launch_reset_capture(const Static &, const State &, unsigned *, int *, hipStream_t);
-void launch_reset_image(const Static &, const State &, const unsigned *, const int *, hipStream_t);
-void launch_py_random_nodes(const unsigned long long *, int, int, int, int, const int *, int *, int *, hipStream_t);      // vds_random.hip
-void launch_start_nodes_check(const int *, int, int, int, int, const int *, int *, unsigned long long *, hipStream_t);
-void launch_tick_main(const Static &, const State &, int, int, hipStream_t);
-void launch_tick_work(const Static &, const State &, int, hipStream_t);
-void launch_update_only(const Static &, const State &, int, hipStream_t);
-void launch_match_dfs(const Static &, const State &, int, hipStream_t);
-void launch_tick_replica2(const Static &, const State &, int, hipStream_t);
-void launch_tick_hybrid(const Static &, const State &, int, int, hipStream_t);
-void emit_tick_rows(const Emit &, const Static &, const State &, int, int, int, int);
-void emit_hybrid_rows(const Emit &, const Static &, const State &, int, int, int, int);
-void emit_hybrid_walk(const Emit &, const Static &, const State &, int, int, int);
-void launch_build_vis(const Static &, const int *, unsigned *, unsigned char *, long long, hipStream_t);
-size_t dfs_walk_lds(const Static &);
-int dfs_walk_pool(const Static &);
-void launch_dispatch(const Static &, const State &, int, int, const int *, const int *, const int *, const int *,
-                     const int *, const int *, const int *, const int *, hipStream_t);
-void launch_dispatch_dense(const Static &, const State &, int, int, const int *, int, hipStream_t);
-void launch_pack_obs(const Static &, const State &, int, int, int, int *, hipStream_t);
-void launch_reduce_counters(const Static &, const State &, long long *, long long *, hipStream_t);
-void launch_selftest_dpp(const int *, int *, int *, int *, int *, int, hipStream_t);
-void set_ablate_tick(int, hipStream_t);
-void read_prof_tick(unsigned long long *, hipStream_t);
-void set_ablate_dfs(int, hipStream_t);
-void read_prof_dfs(unsigned long long *, hipStream_t);
-void set_ablate_dense(int, hipStream_t);
-void read_prof_dense(unsigned long long *, hipStream_t);
-void read_span_dense(unsigned long long *, int, hipStream_t);
-void emit_tick_dense(const Emit &, const Static &, const State &, int, int, int);
-void emit_tick_dense_mixed(const Emit &, const Static &, const State &, int, const int2 *, int);
-bool dense_mixed_ok(const Static &, int);
-void emit_dense_flush(const Emit &, const Static &, const State &, int, int);
-void emit_pack_obs(const Emit &, const Static &, const State &, int, int, int, int *, int, int);
-void emit_dispatch_dense(const Emit &, const Static &, const State &, int, int, const int *, int, int, int);
-void emit_slot_outcomes(const Emit &, const Static &, const State &, int, int, long long *, int, int);
-void launch_slot_outcomes(const Static &, const State &, int, int, long long *, hipStream_t);
-}  // namespace vds
 
 using namespace vds;
 
@@ -275,9 +234,8 @@ struct vds_handle {
     int use_graph = -1;                      // -1: ask VDS_RUN_GRAPH (default on)
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
-    // vds_run of the hybrid neighbour-search tick: replica GROUPS on streams (run_grouped)
-    int run_groups = -1;                     // -1: ask VDS_RUN_GROUPS (default: by replica count, run_group_count)
-    int run_stagger = -1;                    // -1: ask VDS_RUN_STAGGER (default 1)
+    // vds_run / vds_run_hooked: replica GROUPS, launched one after another in the day graph (run_group_count)
+    int run_groups = -1;                     // -1: ask VDS_RUN_GROUPS (default: one)
     // vds_run_hooked: the hooked day (tick -> observations -> policy -> dispatch per slot) as one executable graph, and what it was built for
     hipGraphExec_t hook_exec = nullptr;
     hipGraphExec_t hook_policy_exec = nullptr;   // (eager fallback: the caller's policy graph instantiated by itself)
@@ -462,6 +420,47 @@ static void drop_run_graph(vds_handle *h) {
     }
     h->run_t0 = -1; h->run_n = 0; h->run_G = 1; h->run_stale = false;
 }
+
+// Puts the freshly built g behind *exec and destroys g.  Same shape as the executable graph at hand (new order tables, another first
+// slot): its kernel parameters are replaced in place - no destruction (see the note on day graphs for what that has cost), no
+// instantiation; otherwise `drop` (drop_run_graph / drop_hook_graph) and instantiate.  false: *exec is null, the caller runs eagerly.
+static bool install_graph(vds_handle *h, void (*drop)(vds_handle *), hipGraphExec_t *exec, hipStream_t launched_on, bool same_shape, hipGraph_t g) {
+    bool updated = false;
+    if (*exec && same_shape) {
+        (void)hipStreamSynchronize(launched_on);            // (*exec may still be running there; nullptr = the legacy default stream: valid)
+        hipGraphNode_t bad = nullptr;
+        hipGraphExecUpdateResult res;
+        updated = hipGraphExecUpdate(*exec, g, &bad, &res) == hipSuccess;
+        if (!updated) (void)hipGetLastError();
+    }
+    if (!updated) {
+        drop(h);
+        if (hipGraphInstantiate(exec, g, nullptr, nullptr, 0) != hipSuccess) { *exec = nullptr; (void)hipGetLastError(); }
+    }
+    (void)hipGraphDestroy(g);
+    return *exec != nullptr;
+}
+
+// One chain of launches: on a stream they are issued in order, in a graph every node depends on the one added before it (day graphs
+// are one chain: see the note above).  add(emit_x, args...) calls emit_x(Emit, args...); after a failure the rest is skipped and err
+// says what failed.
+struct Chain {
+    Emit e;
+    hipGraphNode_t tail = nullptr, node = nullptr;
+    hipError_t err = hipSuccess;
+    explicit Chain(hipStream_t st) { e.st = st; }
+    explicit Chain(hipGraph_t g) { e.graph = g; e.node = &node; e.err = &err; }
+    Chain(const Chain &) = delete;
+    template <typename F, typename... A> void add(F emit, A &&...a) {
+        if (err != hipSuccess) return;
+        e.deps = tail ? &tail : nullptr; e.ndeps = tail ? 1 : 0;
+        emit(e, a...);
+        if (e.graph && err == hipSuccess) tail = node;
+    }
+    // (graphs only) a node without work; a captured graph of the caller's as a child graph
+    void add_empty() { add([](const Emit &e) { *e.err = hipGraphAddEmptyNode(e.node, e.graph, e.deps, e.ndeps); }); }
+    void add_child(hipGraph_t child) { add([child](const Emit &e) { *e.err = hipGraphAddChildGraphNode(e.node, e.graph, e.deps, e.ndeps, child); }); }
+};
 
 // lanes per replica of k_tick_dense unless VDS_DENSE_LPR / vds_debug_dense say otherwise
 #ifndef DENSE_LPR_DEFAULT
@@ -1660,7 +1659,7 @@ int vds_num_ticks(const vds_handle *h, int32_t *T) {
 #endif                                  // 11.23 - profiles/r07_cluster_forms/limits.txt: a straggling slow bucket costs more than 16-row workgroups)
 using TickForms = vds_handle::TickForms;
 // the dense tick of slot t, rows [r_lo, r_lo + r_n) (r_n <= 0: to the end)
-static void emit_tick(vds_handle *h, const Emit &e, int t, int r_lo, int r_n) {
+static void emit_tick(const Emit &e, vds_handle *h, int t, int r_lo, int r_n) {
     const TickForms &f = h->forms;
     switch ((size_t)t < f.slot.size() ? f.slot[t].kind : TickForms::BASE) {
     case TickForms::BASE:
@@ -2034,64 +2033,63 @@ static int profile_read_impl(vds_handle *h, float *ms, int32_t cap, int32_t *n) 
     return VDS_OK;
 }
 
-// flush (stamp form, Static.dense_st): pack the lists at once (k_dense_flush) - what a hooked slot needs, since the hook may look at
-// the lists; vds_run leaves it to the next slot's tick and flushes once at the end
+// One replica group of a slot is the chunks (16 replicas: one k_tick_rows workgroup) [chunks * gi / G, chunks * (gi + 1) / G)
+struct Rows { int lo, n; };              // (n <= 0: more groups than chunks - nothing to launch)
+static Rows group_rows(const vds_handle *h, int gi, int G) {
+    const int chunks = (h->S.R + 15) / 16;
+    const int lo = (int)((long long)chunks * gi / G) * 16, hi = (int)((long long)chunks * (gi + 1) / G) * 16;
+    return {lo, std::min(hi, h->S.R) - lo};
+}
+
+// The tick of slot t for the replicas [r_lo, r_lo + r_n) (0, 0: all) in the forms a day graph holds as well as a stream: without
+// neighbour search the row-mapped kernel is the whole tick (k_tick_dense / k_tick_rows); with it Update + own-cluster matching
+// cluster-major (k_tick_dense in stamp form: commits the slot as if nothing were stolen; k_tick_rows in stamp mode on the wide
+// layout), then one workgroup per replica walks the dry orders and commits the slot (k_dfs_walk).
+// flush (stamp form, Static.dense_st): the lists packed at once (k_dense_flush) - what a hooked slot needs, since the hook may look
+// at them; vds_run leaves it to the next slot's tick and flushes once behind the last slot.
+static void slot_tick(Chain &c, vds_handle *h, int t, int r_lo, int r_n, bool flush) {
+    if (!h->dfs_mode) {
+        if (h->S.dense) c.add(emit_tick, h, t, r_lo, r_n);
+        else c.add(emit_tick_rows, h->S, h->D, t, h->lds_ints, r_lo, r_n);
+        return;
+    }
+    if (h->S.dense_st) c.add(emit_tick, h, t, r_lo, r_n);
+    else c.add(emit_hybrid_rows, h->S, h->D, t, h->lds_ints, r_lo, r_n);
+    c.add(emit_hybrid_walk, h->S, h->D, t, r_lo, r_n);
+    if (flush && h->S.dense_st) c.add(emit_dense_flush, h->S, h->D, r_lo, r_n);
+}
+
+static bool run_groups_hybrid(const vds_handle *h) { return h->dfs_mode && h->hybrid_ok && h->cfg.force_generic == 0; }
+
+// One slot on the handle's stream: slot_tick where its forms apply, else the forms only a stream runs - the generic k_tick and the
+// k_tick_work pass, k_tick_replica2 (lower-bound rounds, one workgroup per replica: what the hybrid tick falls back to), the serial
+// reference pair.  Profiling brackets the slot's main launches with two events (not the k_tick_work pass, not the serial pair).
 static int step_impl(vds_handle *h, bool flush = true) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_step: call vds_reset first");
     if (h->last_stepped == h->t) return fail(h, VDS_EINVAL, "vds_step: tick %d already stepped; call vds_advance", h->t);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (h->t >= h->S.T) return fail(h, VDS_EINVAL, "vds_step: tick %d is past the end of the day (%d ticks, :1048)", h->t, h->S.T);
-    if (!h->dfs_mode) {
-        hipEvent_t a = nullptr, b = nullptr;
-        if (h->profiling) {
-            a = next_event(h); b = next_event(h);
-            if (!a || !b) return fail(h, VDS_EHIP, "vds_step: hipEventCreate failed");
-            HIPCHK(h, hipEventRecord(a, h->stream));
-        }
-        if (h->S.dense) {
-            const int rcs = dev_copy_sync(h);
-            if (rcs) return rcs;
-            Emit e; e.st = h->stream; emit_tick(h, e, h->t, 0, 0);
-        }
-        else launch_tick_main(h->S, h->D, h->t, h->lds_ints, h->stream);
-        if (h->profiling) HIPCHK(h, hipEventRecord(b, h->stream));
-        // the fast kernel only defers buckets whose cluster cost block does not fit LDS (wide layout)
-        if (!h->S.dense && (!h->S.fast_ok || h->S.max_nc * h->S.max_nc > h->lds_ints)) launch_tick_work(h->S, h->D, h->t, h->stream);
-    } else if (h->hybrid_ok && h->cfg.force_generic == 0) {
-        // neighbour search, hybrid: Update + own-cluster matching cluster-major (k_tick_rows, stamp mode), then one
-        // workgroup per replica walks the dry orders and commits the slot (k_dfs_walk)
-        hipEvent_t a = nullptr, b = nullptr;
-        if (h->profiling) {
-            a = next_event(h); b = next_event(h);
-            if (!a || !b) return fail(h, VDS_EHIP, "vds_step: hipEventCreate failed");
-            HIPCHK(h, hipEventRecord(a, h->stream));
-        }
-        if (h->S.dense_st) {
-            // ... on the dense layout: k_tick_dense in stamp form commits the slot as if nothing were stolen, k_dfs_walk serves the dry
-            // orders of the replicas that have any and writes out what moved
-            const int rcs = dev_copy_sync(h);
-            if (rcs) return rcs;
-            Emit e; e.st = h->stream;
-            emit_tick(h, e, h->t, 0, 0);
-            emit_hybrid_walk(e, h->S, h->D, h->t, 0, 0);
-            if (flush) emit_dense_flush(e, h->S, h->D, 0, 0);
-        }
-        else launch_tick_hybrid(h->S, h->D, h->t, h->lds_ints, h->stream);
-        if (h->profiling) HIPCHK(h, hipEventRecord(b, h->stream));
-    } else if (h->dfs2_ok && h->cfg.force_generic != 1) {
-        hipEvent_t a = nullptr, b = nullptr;
-        if (h->profiling) {
-            a = next_event(h); b = next_event(h);
-            if (!a || !b) return fail(h, VDS_EHIP, "vds_step: hipEventCreate failed");
-            HIPCHK(h, hipEventRecord(a, h->stream));
-        }
-        // neighbour search: lower-bound rounds, one workgroup per replica (what the hybrid tick falls back to)
-        launch_tick_replica2(h->S, h->D, h->t, h->stream);
-        if (h->profiling) HIPCHK(h, hipEventRecord(b, h->stream));
-    } else {
+    const bool hybrid = run_groups_hybrid(h), replica2 = h->dfs_mode && !hybrid && h->dfs2_ok && h->cfg.force_generic != 1;
+    hipEvent_t a = nullptr, b = nullptr;
+    if (h->profiling && (!h->dfs_mode || hybrid || replica2)) {
+        a = next_event(h); b = next_event(h);
+        if (!a || !b) return fail(h, VDS_EHIP, "vds_step: hipEventCreate failed");
+        HIPCHK(h, hipEventRecord(a, h->stream));
+    }
+    if (h->dfs_mode ? hybrid : (h->S.dense || h->S.fast_ok)) {
+        if (h->dfs_mode ? h->S.dense_st : h->S.dense) { const int rcs = dev_copy_sync(h); if (rcs) return rcs; }
+        Chain c(h->stream);
+        slot_tick(c, h, h->t, 0, 0, flush);
+    }
+    else if (!h->dfs_mode) launch_tick_generic(h->S, h->D, h->t, h->lds_ints, h->stream);
+    else if (replica2) launch_tick_replica2(h->S, h->D, h->t, h->stream);
+    else {
         launch_update_only(h->S, h->D, h->t, h->stream);       // serial reference form
         launch_match_dfs(h->S, h->D, h->t, h->stream);
     }
+    if (b) HIPCHK(h, hipEventRecord(b, h->stream));
+    // the fast kernel only defers buckets whose cluster cost block does not fit LDS (wide layout)
+    if (!h->dfs_mode && !h->S.dense && (!h->S.fast_ok || h->S.max_nc * h->S.max_nc > h->lds_ints)) launch_tick_work(h->S, h->D, h->t, h->stream);
     HIPCHK(h, hipGetLastError());
     h->last_stepped = h->t;
     return VDS_OK;
@@ -2112,29 +2110,30 @@ static int run_eager(vds_handle *h, int32_t n_ticks) {
         if (rc) return rc;
     }
     if (h->S.dense_st && n_ticks > 0) {          // (stamp form: the lists packed once, behind the last slot)
-        Emit e; e.st = h->stream;
-        emit_dense_flush(e, h->S, h->D, 0, 0);
+        Chain c(h->stream);
+        c.add(emit_dense_flush, h->S, h->D, 0, 0);
         HIPCHK(h, hipGetLastError());
     }
     return VDS_OK;
 }
 
-// ---- vds_run: replica groups, launched one after another in the day graph (they were parallel branches: see the note on day graphs).
+// ---- vds_run: replica groups, launched one after another in the day graph.
 // One hybrid tick = k_tick_rows in stamp mode (VALU-bound, fills the chip) + k_dfs_walk (one workgroup per replica, a
 // dependency chain of ~50 dry orders: ~150 us whatever the replica count, the CUs mostly idle).  Replicas never interact, so
-// the replicas are split into G groups (boundaries at multiples of 16 = one k_tick_rows workgroup) and every group runs its own
-// chain rows(t) -> walk(t) -> rows(t + 1) -> ... as a branch of the graph: the rows kernel of one group executes under the
-// walks of the others.  stagger 2: the rows kernels are serialised round-robin over the groups by extra edges (rows of group
-// g after the rows of group g - 1; group 0 after the last group's rows of the previous tick); 1 (default): only the first
-// tick is staggered that way, then the groups run free; 0: free-running from the start.  (Measured: 1 = 0 >= 2.)
-// Hooked stepping (vds_step) stays one launch pair over all replicas: the hook needs every replica at the same slot.
-// The plain tick (no neighbour search: ONE k_tick_rows per tick) is grouped as well - two chains of half-size launches instead
-// of one chain: a launch of one group fills the drain / fill bubbles at the kernel boundaries of the other and the two run out of
-// phase on every SIMD (one chain: the seven workgroups of a CU start together, load together, compute together).
-static bool run_groups_hybrid(const vds_handle *h) { return h->dfs_mode && h->hybrid_ok && h->cfg.force_generic == 0; }
+// the replicas can be split into G groups (group_rows) with launches of their own.  The groups were made to run as parallel
+// branches of the graph - the rows kernel of one under the walks of the others: 7-9 %, profiles/r03_run_groups/notes.md - and parallel
+// branches are not used any more (the note on day graphs says why): the groups of a slot are nodes of the one chain, rows(t, 0) ->
+// walk(t, 0) -> rows(t, 1) -> walk(t, 1) -> rows(t + 1, 0) -> ..., which only adds launches.  So one group is the default, more
+// come on request only (vds_set_run_groups, VDS_RUN_GROUPS), and results do not depend on the grouping.
+// The plain tick (no neighbour search: ONE kernel per tick) is grouped the same way.  Hooked stepping (vds_step) stays one launch
+// pair over all replicas: the hook needs every replica at the same slot.
 static bool run_groups_plain(const vds_handle *h) {
     // (the fast kernel alone: every cost block fits LDS - no k_tick_work pass)
     return !h->dfs_mode && h->S.fast_ok && (h->S.dense || h->S.max_nc * h->S.max_nc <= h->lds_ints);
+}
+static bool run_graph_on(vds_handle *h) {        // VDS_RUN_GRAPH=0: no day graphs, every slot launched on the stream
+    if (h->use_graph < 0) { const char *v = getenv("VDS_RUN_GRAPH"); h->use_graph = (v && *v == '0') ? 0 : 1; }
+    return h->use_graph != 0;
 }
 static int run_group_count(vds_handle *h) {
     // (replicas stored regrouped by day - Static.rperm - are grouped like any others: the row map is the identity on the
@@ -2144,11 +2143,7 @@ static int run_group_count(vds_handle *h) {
         const char *v = getenv("VDS_RUN_GROUPS");
         h->run_groups = (v && *v) ? atoi(v) : 0;
     }
-    if (h->run_stagger < 0) {
-        const char *v = getenv("VDS_RUN_STAGGER");
-        h->run_stagger = (v && *v) ? atoi(v) : 1;
-    }
-    if (!h->use_graph) return 1;             // (groups only as branches of the day's graph: see vds_run)
+    if (!run_graph_on(h)) return 1;          // (groups only as launches of the day's graph: see vds_run)
     int G = h->run_groups > 0 ? h->run_groups : 1;
     const int chunks = (h->S.R + 15) / 16;
     if (G > chunks) G = chunks;
@@ -2156,65 +2151,35 @@ static int run_group_count(vds_handle *h) {
     return G < 1 ? 1 : G;
 }
 
-// the day graph with the replica groups one after another, built node by node (kernel nodes with explicit dependencies; no
-// streams or events are involved)
+// the day graph with the replica groups one after another, built node by node (no streams or events are involved); a group's
+// lists (stamp form) are packed behind its last slot
 static int build_group_graph(vds_handle *h, int32_t n_ticks, int G, hipGraph_t *out) {
     hipGraph_t g = nullptr;
     HIPCHK(h, hipGraphCreate(&g, 0));
-    const int chunks = (h->S.R + 15) / 16;
-    hipGraphNode_t prev = nullptr;                      // every node after the one emitted before it: one chain, no parallel branches
-    hipError_t err = hipSuccess;
-    for (int i = 0; i < n_ticks && err == hipSuccess; ++i) {
-        const int t = h->t + i;
-        for (int gi = 0; gi < G && err == hipSuccess; ++gi) {
-            const int c0 = (int)((long long)chunks * gi / G), c1 = (int)((long long)chunks * (gi + 1) / G);
-            const int r_lo = c0 * 16, r_n = (c1 * 16 < h->S.R ? c1 * 16 : h->S.R) - r_lo;
-            if (r_n <= 0) continue;
-            hipGraphNode_t node = nullptr;
-            Emit e;
-            e.graph = g; e.deps = prev ? &prev : nullptr; e.ndeps = prev ? 1 : 0; e.node = &node; e.err = &err;
-            if (!h->dfs_mode) {                 // plain tick: the row-mapped kernel is the whole tick
-                if (h->S.dense) emit_tick(h, e, t, r_lo, r_n);
-                else emit_tick_rows(e, h->S, h->D, t, h->lds_ints, r_lo, r_n);
-                if (err != hipSuccess) break;
-                prev = node;
-                continue;
-            }
-            if (h->S.dense_st) emit_tick(h, e, t, r_lo, r_n);          // (stamp form)
-            else emit_hybrid_rows(e, h->S, h->D, t, h->lds_ints, r_lo, r_n);
-            if (err != hipSuccess) break;
-            prev = node;
-            e.deps = &prev; e.ndeps = 1; e.node = &node;
-            emit_hybrid_walk(e, h->S, h->D, t, r_lo, r_n);
-            if (err != hipSuccess) break;
-            prev = node;
-            if (h->S.dense_st && i == n_ticks - 1) {              // the group's lists packed behind its last slot
-                e.deps = &prev; e.ndeps = 1; e.node = &node;
-                emit_dense_flush(e, h->S, h->D, r_lo, r_n);
-                if (err != hipSuccess) break;
-                prev = node;
-            }
+    Chain c(g);
+    for (int i = 0; i < n_ticks; ++i)
+        for (int gi = 0; gi < G; ++gi) {
+            const Rows r = group_rows(h, gi, G);
+            if (r.n > 0) slot_tick(c, h, h->t + i, r.lo, r.n, i == n_ticks - 1);
         }
-    }
-    if (err != hipSuccess) {
+    if (c.err != hipSuccess) {
         (void)hipGraphDestroy(g);
         (void)hipGetLastError();
-        return fail(h, VDS_EHIP, "vds_run: hipGraphAddKernelNode failed: %s", hipGetErrorString(err));
+        return fail(h, VDS_EHIP, "vds_run: hipGraphAddKernelNode failed: %s", hipGetErrorString(c.err));
     }
     *out = g;
     return VDS_OK;
 }
 
-// SimCity's loop without hooks (:1048-1091) for n_ticks slots.  Runs of 8 slots and more are captured once as a hipGraph
-// (stream capture of the launches) and replayed afterwards: one submission per day instead of 148 / 296.
-// VDS_RUN_GRAPH=0 keeps the eager loop.  The replica groups (on request) are launches of that graph
-// (build_group_graph) and exist ONLY there: issued eagerly on streams, the cross-stream event waits of a grouped day made the
+// SimCity's loop without hooks (:1048-1091) for n_ticks slots.  Runs of 8 slots and more become a hipGraph once (one group: stream
+// capture of run_eager's launches, which keeps every form step_impl knows; more: build_group_graph) and are replayed afterwards: one
+// submission per day instead of 148 / 296.  VDS_RUN_GRAPH=0 keeps the eager loop.  The replica groups (on request) are launches of
+// that graph and exist ONLY there: issued eagerly on streams, the cross-stream event waits of a grouped day made the
 // HIP runtime of this image abort in free() (profiles/r03_run_groups/notes.md), so the eager path keeps one launch pair per
 // tick over all replicas.
 int vds_run(vds_handle *h, int32_t n_ticks) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_run: call vds_reset first");
-    if (h->use_graph < 0) { const char *v = getenv("VDS_RUN_GRAPH"); h->use_graph = (v && *v == '0') ? 0 : 1; }
-    if (!h->use_graph || h->profiling || n_ticks < 8 || h->last_stepped == h->t || h->t + n_ticks > h->S.T) return run_eager(h, n_ticks);
+    if (!run_graph_on(h) || h->profiling || n_ticks < 8 || h->last_stepped == h->t || h->t + n_ticks > h->S.T) return run_eager(h, n_ticks);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     { const int rcs = dev_copy_sync(h); if (rcs) return rcs; }
     const int G = run_group_count(h);
@@ -2237,22 +2202,7 @@ int vds_run(vds_handle *h, int32_t n_ticks) {
             if (rc) return rc;
             return run_eager(h, n_ticks);
         }
-        // same shape as the graph at hand (new order tables, another first slot): its kernel parameters are replaced in place -
-        // no destruction (see drop_run_graph for what that costs), no instantiation
-        bool updated = false;
-        if (h->run_exec && h->run_n == n_ticks && h->run_G == G) {
-            (void)hipStreamSynchronize(h->run_stream);          // (run_exec was launched there; nullptr = legacy default stream)
-            hipGraphNode_t bad = nullptr;
-            hipGraphExecUpdateResult res;
-            updated = hipGraphExecUpdate(h->run_exec, g, &bad, &res) == hipSuccess;
-            if (!updated) (void)hipGetLastError();
-        }
-        if (!updated) {
-            drop_run_graph(h);
-            const hipError_t ei = hipGraphInstantiate(&h->run_exec, g, nullptr, nullptr, 0);
-            if (ei != hipSuccess) { (void)hipGraphDestroy(g); h->run_exec = nullptr; (void)hipGetLastError(); return run_eager(h, n_ticks); }
-        }
-        (void)hipGraphDestroy(g);
+        if (!install_graph(h, drop_run_graph, &h->run_exec, h->run_stream, h->run_n == n_ticks && h->run_G == G, g)) return run_eager(h, n_ticks);
         h->run_t0 = t0; h->run_n = n_ticks; h->run_stream = h->stream; h->run_G = G; h->run_stale = false;
     }
     HIPCHK(h, hipGraphLaunch(h->run_exec, h->stream));
@@ -2264,17 +2214,16 @@ int vds_run(vds_handle *h, int32_t n_ticks) {
 // the group count vds_run uses for this handle as it stands (1: one launch pair per tick over all replicas)
 int vds_get_run_groups(vds_handle *h) {
     if (!h || !h->have_static) return 1;
-    if (h->use_graph < 0) { const char *v = getenv("VDS_RUN_GRAPH"); h->use_graph = (v && *v == '0') ? 0 : 1; }
     return run_group_count(h);
 }
 
-// Scheduling knob of vds_run in hybrid neighbour-search mode (no reference counterpart): groups <= 0 restores the default.
+// Scheduling knob of vds_run / vds_run_hooked (no reference counterpart): groups <= 0 restores the default.  stagger ordered the
+// groups while they were parallel branches of the day graph: it is still accepted (0 / 1 / 2, or negative) and has no effect.
 int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger) {
     if (!h) return VDS_EINVAL;
     if (groups > RUN_GROUPS_MAX || stagger > 2) return fail(h, VDS_EINVAL, "vds_set_run_groups: groups <= %d, stagger 0 / 1 / 2 (or negative: default)", RUN_GROUPS_MAX);
     { h->run_stale = true; h->tables_gen++; }
     h->run_groups = groups > 0 ? groups : -1;
-    h->run_stagger = stagger >= 0 ? stagger : -1;
     return VDS_OK;
 }
 
@@ -2282,9 +2231,9 @@ int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger) {
 // SupplyExpect, :1053-1076), the observation planes into the library's block (vds_obs_device_planes), the caller's policy - a captured
 // graph that reads the block and writes the action tensor, embedded as a child graph; or none -, the actions applied
 // (vds_apply_dispatch_device: the DispatchFunction body, :1083), the next slot (:1090-1091).  The whole run is ONE executable graph:
-// one submission per call instead of three or four launches per slot, and - like vds_run - the replicas as groups in parallel
-// branches, so that the small latency-bound kernels of one group (observations, dispatch) run under the tick of the other.  The
-// policy node, which sees all replicas, joins the branches once per slot.
+// one submission per call instead of three or four launches per slot.  Like vds_run's it is one chain of nodes; replica groups (on
+// request only, see below) are launches of that chain, and the policy node, which sees all replicas, comes behind the last group's
+// planes and before the first group's dispatch.
 static int ensure_outcomes(vds_handle *h);
 
 static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
@@ -2314,9 +2263,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     if (n_ticks == 0) return VDS_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (planes & VDS_PLANE_OUTCOMES) { const int rco = ensure_outcomes(h); if (rco) return rco; }
-    if (h->use_graph < 0) { const char *v = getenv("VDS_RUN_GRAPH"); h->use_graph = (v && *v == '0') ? 0 : 1; }
     const bool groupable = run_groups_hybrid(h) || run_groups_plain(h);
-    if (!h->use_graph || h->profiling || !groupable) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
+    if (!run_graph_on(h) || h->profiling || !groupable) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
     { const int rcs = dev_copy_sync(h); if (rcs) return rcs; }
     // replica groups only when the caller asked for them (vds_set_run_groups): measured at configs[1], the
     // hooked day is FASTER as one chain (69.8 / 72.6 / 76.1 us per slot with 1 / 2 / 3 groups, profiles/r05/hooked_groups.txt - the
@@ -2329,98 +2277,37 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     if (!same) {
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
-        const int chunks = (h->S.R + 15) / 16;
-        hipGraphNode_t chain = nullptr;         // every node after the one emitted before it: one chain, no parallel branches
-        hipError_t err = hipSuccess;
-        for (int i = 0; i < n_ticks && err == hipSuccess; ++i) {
+        Chain c(g);
+        for (int i = 0; i < n_ticks; ++i) {
             const int t = h->t + i;
-            for (int gi = 0; gi < G && err == hipSuccess; ++gi) {
-                const int c0 = (int)((long long)chunks * gi / G), c1 = (int)((long long)chunks * (gi + 1) / G);
-                const int r_lo = c0 * 16, r_n = (c1 * 16 < h->S.R ? c1 * 16 : h->S.R) - r_lo;
-                if (r_n <= 0) continue;
-                hipGraphNode_t n1 = nullptr, n2 = nullptr, n3 = nullptr;
-                Emit e;
-                e.graph = g; e.deps = chain ? &chain : nullptr; e.ndeps = chain ? 1 : 0; e.node = &n1; e.err = &err;
-                if (!h->dfs_mode) {
-                    if (h->S.dense) emit_tick(h, e, t, r_lo, r_n);
-                    else emit_tick_rows(e, h->S, h->D, t, h->lds_ints, r_lo, r_n);
-                } else {
-                    if (h->S.dense_st) emit_tick(h, e, t, r_lo, r_n);
-                    else emit_hybrid_rows(e, h->S, h->D, t, h->lds_ints, r_lo, r_n);
-                    if (err != hipSuccess) break;
-                    e.deps = &n1; e.ndeps = 1; e.node = &n2;
-                    emit_hybrid_walk(e, h->S, h->D, t, r_lo, r_n);
-                    n1 = n2;
-                    if (h->S.dense_st && err == hipSuccess) {      // (stamp form: the hook may look at the lists - packed now)
-                        hipGraphNode_t nf = nullptr;
-                        e.deps = &n1; e.ndeps = 1; e.node = &nf;
-                        emit_dense_flush(e, h->S, h->D, r_lo, r_n);
-                        n1 = nf;
-                    }
-                }
-                if (err != hipSuccess) break;
-                chain = n1;
-                if (planes & 31) {
-                    e.deps = &chain; e.ndeps = 1; e.node = &n3;
-                    emit_pack_obs(e, h->S, h->D, t, 1, planes & 31, h->d_obs, r_lo, r_n);
-                    if (err != hipSuccess) break;
-                    chain = n3;
-                }
-                if (planes & VDS_PLANE_OUTCOMES) {          // the slot's per-cluster order outcomes, behind the group's last tick launch
-                    hipGraphNode_t n4 = nullptr;
-                    e.deps = &chain; e.ndeps = 1; e.node = &n4;
-                    emit_slot_outcomes(e, h->S, h->D, t, 1, h->d_outc, r_lo, r_n);
-                    if (err != hipSuccess) break;
-                    chain = n4;
-                }
+            for (int gi = 0; gi < G; ++gi) {
+                const Rows r = group_rows(h, gi, G);
+                if (r.n <= 0) continue;
+                slot_tick(c, h, t, r.lo, r.n, true);        // (stamp form: the hook may look at the lists - packed now)
+                if (planes & 31) c.add(emit_pack_obs, h->S, h->D, t, 1, planes & 31, h->d_obs, r.lo, r.n);
+                // the slot's per-cluster order outcomes, behind the group's last tick launch
+                if (planes & VDS_PLANE_OUTCOMES) c.add(emit_slot_outcomes, h->S, h->D, t, 1, h->d_outc, r.lo, r.n);
             }
-            if (err != hipSuccess) break;
             if (policy_graph) {
                 // (the child graph between two EMPTY nodes: with several parents / several children attached to the child-graph node
                 // itself the runtime of this image started it after the first parent - actions computed from observations of the slot before)
-                hipGraphNode_t join = nullptr, pol = nullptr, fork = nullptr;
-                err = hipGraphAddEmptyNode(&join, g, chain ? &chain : nullptr, chain ? 1 : 0);
-                if (err != hipSuccess) break;
-                err = hipGraphAddChildGraphNode(&pol, g, &join, 1, (hipGraph_t)policy_graph);
-                if (err != hipSuccess) break;
-                err = hipGraphAddEmptyNode(&fork, g, &pol, 1);
-                if (err != hipSuccess) break;
-                chain = fork;
+                c.add_empty();
+                c.add_child((hipGraph_t)policy_graph);
+                c.add_empty();
             }
-            for (int gi = 0; gi < G && err == hipSuccess && K > 0; ++gi) {
-                const int c0 = (int)((long long)chunks * gi / G), c1 = (int)((long long)chunks * (gi + 1) / G);
-                const int r_lo = c0 * 16, r_n = (c1 * 16 < h->S.R ? c1 * 16 : h->S.R) - r_lo;
-                if (r_n <= 0) continue;
-                hipGraphNode_t nd = nullptr;
-                Emit e;
-                e.graph = g; e.deps = chain ? &chain : nullptr; e.ndeps = chain ? 1 : 0; e.node = &nd; e.err = &err;
-                emit_dispatch_dense(e, h->S, h->D, t, K, (const int *)dev_actions, 0, r_lo, r_n);
-                if (err != hipSuccess) break;
-                chain = nd;
+            for (int gi = 0; gi < G && K > 0; ++gi) {
+                const Rows r = group_rows(h, gi, G);
+                if (r.n > 0) c.add(emit_dispatch_dense, h->S, h->D, t, K, (const int *)dev_actions, 0, r.lo, r.n);
             }
         }
-        if (err != hipSuccess) {
+        if (c.err != hipSuccess) {
             (void)hipGraphDestroy(g);
             (void)hipGetLastError();
-            return fail(h, VDS_EHIP, "vds_run_hooked: building the day graph failed: %s", hipGetErrorString(err));
+            return fail(h, VDS_EHIP, "vds_run_hooked: building the day graph failed: %s", hipGetErrorString(c.err));
         }
-        bool updated = false;
-        if (h->hook_exec && h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) && (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr)) {
-            (void)hipStreamSynchronize(h->hook_stream);
-            hipGraphNode_t bad = nullptr;
-            hipGraphExecUpdateResult res;
-            updated = hipGraphExecUpdate(h->hook_exec, g, &bad, &res) == hipSuccess;
-            if (!updated) (void)hipGetLastError();
-        }
-        if (!updated) {
-            drop_hook_graph(h);
-            const hipError_t ei = hipGraphInstantiate(&h->hook_exec, g, nullptr, nullptr, 0);
-            if (ei != hipSuccess) {
-                (void)hipGraphDestroy(g); h->hook_exec = nullptr; (void)hipGetLastError();
-                return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
-            }
-        }
-        (void)hipGraphDestroy(g);
+        const bool same_shape = h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) &&
+                                (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr);
+        if (!install_graph(h, drop_hook_graph, &h->hook_exec, h->hook_stream, same_shape, g)) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
         h->hook_t0 = h->t; h->hook_n = n_ticks; h->hook_G = G; h->hook_planes = planes; h->hook_K = K; h->hook_actions = dev_actions;
         h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen; h->hook_outc = h->d_outc;
     }

@@ -174,6 +174,17 @@ struct Emit {
     hipGraphNode_t *node = nullptr;
     hipError_t *err = nullptr;
 };
+// ... and the one place that does either.  The arguments are taken by value in the kernel's own parameter types (P is deduced from
+// the kernel alone), so that a graph node gets the address of exactly what a stream launch would pass.
+template <typename T> struct emit_arg { using type = T; };
+template <typename... P>
+static inline void emit_kernel(const Emit &e, void (*k)(P...), dim3 grid, dim3 block, size_t lds, typename emit_arg<P>::type... a) {
+    if (!e.graph) { hipLaunchKernelGGL(k, grid, block, lds, e.st, a...); return; }
+    void *args[] = {(void *)&a...};
+    hipKernelNodeParams p{};
+    p.func = reinterpret_cast<void *>(k); p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = (unsigned)lds; p.kernelParams = args; p.extra = nullptr;
+    *e.err = hipGraphAddKernelNode(e.node, e.graph, e.deps, e.ndeps, &p);
+}
 
 struct State {
     int *hdr;

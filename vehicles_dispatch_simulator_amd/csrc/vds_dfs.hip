@@ -5,6 +5,7 @@
 //   k_match_dfs    the serial reference form (one wavefront walks a replica's orders in id order): last fallback and a second,
 //                  independent GPU statement for the tests
 #include "vds_kernels_common.h"
+#include "vds_launch.h"
 
 namespace vds {
 
@@ -2106,8 +2107,6 @@ void launch_build_vis(const Static &S, const int *so_bkt0, unsigned *so_vis, uns
     hipLaunchKernelGGL(k_build_vis, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S, so_bkt0, so_vis, so_lb, n_orders);
 }
 
-void launch_hybrid_rows(const Static &S, const State &D, int t, int lds_ints, hipStream_t st, int r_lo, int r_n);      // vds_tick.hip
-
 void launch_tick_replica2(const Static &S, const State &D, int t, hipStream_t st) {
     const size_t lds = replica2_lds_ints(S.C, S.V, S.max_tick_orders) * sizeof(int);
     if (S.u8_ok) hipLaunchKernelGGL(k_tick_replica2<true>, dim3(S.R), dim3(REPL_THREADS), lds, st, S, D, t);
@@ -2122,38 +2121,19 @@ int dfs_walk_pool(const Static &S) {
     return ns;
 }
 
-static void emit_walk(const Emit &e, void (*k)(Static, State, int), dim3 grid, dim3 block, size_t lds, Static S, State D, int t) {
-    if (!e.graph) { hipLaunchKernelGGL(k, grid, block, lds, e.st, S, D, t); return; }
-    void *args[3] = {&S, &D, &t};
-    hipKernelNodeParams p{};
-    p.func = reinterpret_cast<void *>(k); p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = (unsigned)lds; p.kernelParams = args; p.extra = nullptr;
-    *e.err = hipGraphAddKernelNode(e.node, e.graph, e.deps, e.ndeps, &p);
-}
-
-// second half of the hybrid neighbour-search tick for the replicas [r_lo, r_lo + r_n) (r_n = 0: all).  vds_run launches the tick
-// per GROUP of replicas as parallel branches of the day graph, so that the stamp-mode kernel of one group (VALU-bound) runs
-// under the walk of another (a per-replica dependency chain that leaves the CUs mostly idle).
+// second half of the hybrid neighbour-search tick for the replicas [r_lo, r_lo + r_n) (r_n = 0: all): a replica group of a day graph
+// (vds_api.hip: the groups of a slot run one after another), or all of them
 void emit_hybrid_walk(const Emit &e, const Static &S0, const State &D, int t, int r_lo, int r_n) {
     Static S = S0;
     S.r_lo = r_lo;
     const dim3 grid(r_n > 0 ? r_n : S.R);
     if (S.dense_st) {
         // the dense layout's walk (byte costs: vds_api.hip grants the stamp form only then)
-        emit_walk(e, S.seq_pad <= 64 ? k_dfs_walk<true, 1, true> : (S.seq_pad <= 128 ? k_dfs_walk<true, 2, true> : k_dfs_walk<true, 4, true>), grid, dim3(WK_THREADS), dfs_walk_lds(S), S, D, t);
+        emit_kernel(e, S.seq_pad <= 64 ? k_dfs_walk<true, 1, true> : (S.seq_pad <= 128 ? k_dfs_walk<true, 2, true> : k_dfs_walk<true, 4, true>), grid, dim3(WK_THREADS), dfs_walk_lds(S), S, D, t);
         return;
     }
-    if (S.u8_ok) emit_walk(e, S.seq_pad <= 64 ? k_dfs_walk<true, 1> : (S.seq_pad <= 128 ? k_dfs_walk<true, 2> : k_dfs_walk<true, 4>), grid, dim3(WK_THREADS), dfs_walk_lds(S), S, D, t);
-    else emit_walk(e, S.seq_pad <= 64 ? k_dfs_walk<false, 1> : (S.seq_pad <= 128 ? k_dfs_walk<false, 2> : k_dfs_walk<false, 4>), grid, dim3(WK_THREADS), dfs_walk_lds(S), S, D, t);
-}
-
-void launch_hybrid_walk(const Static &S, const State &D, int t, hipStream_t st, int r_lo, int r_n) {
-    Emit e; e.st = st;
-    emit_hybrid_walk(e, S, D, t, r_lo, r_n);
-}
-
-void launch_tick_hybrid(const Static &S, const State &D, int t, int lds_ints, hipStream_t st) {
-    launch_hybrid_rows(S, D, t, lds_ints, st, 0, 0);
-    launch_hybrid_walk(S, D, t, st, 0, 0);
+    if (S.u8_ok) emit_kernel(e, S.seq_pad <= 64 ? k_dfs_walk<true, 1> : (S.seq_pad <= 128 ? k_dfs_walk<true, 2> : k_dfs_walk<true, 4>), grid, dim3(WK_THREADS), dfs_walk_lds(S), S, D, t);
+    else emit_kernel(e, S.seq_pad <= 64 ? k_dfs_walk<false, 1> : (S.seq_pad <= 128 ? k_dfs_walk<false, 2> : k_dfs_walk<false, 4>), grid, dim3(WK_THREADS), dfs_walk_lds(S), S, D, t);
 }
 
 void launch_match_dfs(const Static &S, const State &D, int t, hipStream_t st) {

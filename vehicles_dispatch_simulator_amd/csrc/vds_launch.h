@@ -1,0 +1,55 @@
+// Host-side launchers of the kernel files, as vds_api.hip calls them: declarations only (included by vds_api.hip and by every file that
+// defines one of them; hashed with the HOST sources: Makefile).
+//   launch_*  on a stream
+//   emit_*    on a stream or as a kernel node of an explicitly built hipGraph (Emit, vds_device.h), for the replicas
+//             [r_lo, r_lo + r_n) - r_lo a multiple of 16; r_n <= 0 (with r_lo 0): all
+#pragma once
+#include "vds_device.h"
+
+namespace vds {
+// ---- vds_tick.hip
+void launch_reset(const Static &S, const State &D, const int *veh_node, hipStream_t st);
+bool reset_uses_image(const Static &S);
+void launch_reset_capture(const Static &S, const State &D, unsigned *img, int *base, hipStream_t st);
+void launch_reset_image(const Static &S, const State &D, const unsigned *img, const int *base, hipStream_t st);
+void launch_tick_generic(const Static &S, const State &D, int t, int lds_ints, hipStream_t st);
+void launch_tick_work(const Static &S, const State &D, int t, hipStream_t st);
+void launch_update_only(const Static &S, const State &D, int t, hipStream_t st);
+void emit_tick_rows(const Emit &e, const Static &S, const State &D, int t, int lds_ints, int r_lo, int r_n);
+void emit_hybrid_rows(const Emit &e, const Static &S, const State &D, int t, int lds_ints, int r_lo, int r_n);
+void launch_dispatch(const Static &S, const State &D, int t, int ngroups, const int *grp_off, const int *a_replica, const int *a_cluster,
+                     const int *a_pos, const int *a_target, const int *a_seq, const int *a_arrive, const int *a_counted, hipStream_t st);
+void emit_dispatch_dense(const Emit &e, const Static &S, const State &D, int t, int K, const int *actions, int seq_base, int r_lo, int r_n);
+void launch_dispatch_dense(const Static &S, const State &D, int t, int K, const int *actions, int seq_base, hipStream_t st);
+void emit_pack_obs(const Emit &e, const Static &S, const State &D, int t, int stepped, int planes, int *obs, int r_lo, int r_n);
+void launch_pack_obs(const Static &S, const State &D, int t, int stepped, int planes, int *obs, hipStream_t st);
+void launch_reduce_counters(const Static &S, const State &D, long long *per, long long *tot, hipStream_t st);
+void launch_selftest_dpp(const int *in, int *o0, int *o1, int *o2, int *o3, int nwaves, hipStream_t st);
+void set_ablate_tick(int flags, hipStream_t st);
+void read_prof_tick(unsigned long long *out, hipStream_t st);
+// ---- vds_tick_dense.hip
+void emit_tick_dense(const Emit &e, const Static &S, const State &D, int t, int r_lo, int r_n);
+void emit_tick_dense_mixed(const Emit &e, const Static &S, const State &D, int t, const int2 *bmap, int nblk);
+bool dense_mixed_ok(const Static &S, int slots);
+void emit_dense_flush(const Emit &e, const Static &S, const State &D, int r_lo, int r_n);
+void set_ablate_dense(int flags, hipStream_t st);
+void read_prof_dense(unsigned long long *out, hipStream_t st);
+void read_span_dense(unsigned long long *out, int reset, hipStream_t st);
+// ---- vds_dfs.hip
+void launch_match_dfs(const Static &S, const State &D, int t, hipStream_t st);
+void launch_tick_replica2(const Static &S, const State &D, int t, hipStream_t st);
+void emit_hybrid_walk(const Emit &e, const Static &S, const State &D, int t, int r_lo, int r_n);
+void launch_build_vis(const Static &S, const int *so_bkt0, unsigned *so_vis, unsigned char *so_lb, long long n_orders, hipStream_t st);
+size_t dfs_walk_lds(const Static &S);
+int dfs_walk_pool(const Static &S);
+void set_ablate_dfs(int flags, hipStream_t st);
+void read_prof_dfs(unsigned long long *out, hipStream_t st);
+// ---- vds_random.hip
+void launch_py_random_nodes(const unsigned long long *seeds, int R, int N, int V, int C, const int *node2cluster, int *veh_node, int *fullest,
+                            hipStream_t st);
+void launch_start_nodes_check(const int *veh_node, int R, int N, int V, int C, const int *node2cluster, int *fullest, unsigned long long *bad,
+                              hipStream_t st);
+// ---- vds_outcomes.hip
+void emit_slot_outcomes(const Emit &e, const Static &S, const State &D, int t, int stepped, long long *oc, int r_lo, int r_n);
+void launch_slot_outcomes(const Static &S, const State &D, int t, int stepped, long long *oc, hipStream_t st);
+}  // namespace vds

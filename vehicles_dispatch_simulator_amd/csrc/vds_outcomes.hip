@@ -17,6 +17,7 @@
 // The quirk-Q1 order that is never processed (:914-915) has no sorted position: it is in no bucket.
 // This file is hashed with the HOST sources (Makefile): it is not one of the tick kernels the profiles/ evidence refers to.
 #include "vds_kernels_common.h"
+#include "vds_launch.h"
 
 namespace vds {
 
@@ -102,16 +103,10 @@ static int outcome_lanes(const Static &S) {
 void emit_slot_outcomes(const Emit &e, const Static &S0, const State &D, int t, int stepped, long long *oc, int r_lo, int r_n) {
     Static S = S0;
     S.r_lo = r_lo;
-    int lpb = outcome_lanes(S);
+    const int lpb = outcome_lanes(S);
     const int per = OC_THREADS / lpb, n = r_n > 0 ? r_n : S.R - r_lo;
-    int r_end = r_lo + n;
     const dim3 grid((S.C + per - 1) / per, (n + OC_RPT - 1) / OC_RPT), block(OC_THREADS);
-    if (!e.graph) { hipLaunchKernelGGL(k_slot_outcomes, grid, block, 0, e.st, S, D, t, stepped, lpb, r_end, oc); return; }
-    State Dv = D;
-    void *args[7] = {&S, &Dv, &t, &stepped, &lpb, &r_end, &oc};
-    hipKernelNodeParams p{};
-    p.func = reinterpret_cast<void *>(k_slot_outcomes); p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = 0; p.kernelParams = args; p.extra = nullptr;
-    *e.err = hipGraphAddKernelNode(e.node, e.graph, e.deps, e.ndeps, &p);
+    emit_kernel(e, k_slot_outcomes, grid, block, 0, S, D, t, stepped, lpb, r_lo + n, oc);
 }
 
 void launch_slot_outcomes(const Static &S, const State &D, int t, int stepped, long long *oc, hipStream_t st) {

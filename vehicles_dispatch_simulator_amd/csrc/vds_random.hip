@@ -14,6 +14,7 @@
 // The kernel also counts the replica's vehicles per cluster (LDS histogram) and reports the fullest start list, which vds_reset
 // derives from the caller's array on the host to size the idle tables.
 // This file is hashed with the HOST sources (Makefile): it is not one of the tick kernels the profiles/ evidence refers to.
+#include "vds_launch.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

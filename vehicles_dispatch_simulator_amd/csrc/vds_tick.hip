@@ -27,6 +27,7 @@
 // "lowest position wins": a match is a row-wide DPP min-reduction of (cost << 7 | position).
 // No MFMA: this is index / gather / scan work.
 #include "vds_kernels_common.h"
+#include "vds_launch.h"
 
 namespace vds {
 
@@ -1457,15 +1458,8 @@ void launch_reset(const Static &S, const State &D, const int *veh_node, hipStrea
 
 static int rows_lds_bytes(int lds_ints) { return 64 * 16 + ROWS_WAVES * 4 * ROW_KEYS * 8 + (ROWS_PF ? ROWS_PF_BYTES : 0) + lds_ints * 4; }
 
-// Emit: the same launch either goes to a stream or becomes a kernel node of an explicitly built hipGraph - vds_run's day graph
-// with the replica groups as parallel branches is built node by node, not captured from forked streams.
-static void emit_rows(const Emit &e, void (*k)(Static, State, int, int), dim3 grid, dim3 block, size_t lds, Static S, State D, int t, int li) {
-    if (!e.graph) { hipLaunchKernelGGL(k, grid, block, lds, e.st, S, D, t, li); return; }
-    void *args[4] = {&S, &D, &t, &li};
-    hipKernelNodeParams p{};
-    p.func = reinterpret_cast<void *>(k); p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = (unsigned)lds; p.kernelParams = args; p.extra = nullptr;
-    *e.err = hipGraphAddKernelNode(e.node, e.graph, e.deps, e.ndeps, &p);
-}
+// (Emit / emit_kernel, vds_device.h: the same launch goes to a stream or becomes a kernel node of an explicitly built hipGraph - the
+// day graphs of vds_run with replica groups and of vds_run_hooked are built node by node, not captured)
 
 // the row-mapped kernel for the replicas [r_lo, r_lo + r_n) (r_lo a multiple of 16; r_n = 0: all), on a stream or as a graph node
 void emit_tick_rows(const Emit &e, const Static &S0, const State &D, int t, int lds_ints, int r_lo, int r_n) {
@@ -1477,19 +1471,14 @@ void emit_tick_rows(const Emit &e, const Static &S0, const State &D, int t, int 
     const dim3 grid(S.C * rchunks), block(ROWS_WAVES * WAVE);
     if (S.u8_ok) {
         const int li = min(lds_ints, (S.max_nc * S.max_nc + 15) / 16 * 4);      // byte blocks: a quarter of the LDS
-        emit_rows(e, dm == 2 ? k_tick_rows<true, 2> : (dm == 1 ? k_tick_rows<true, 1> : k_tick_rows<true, 0>), grid, block, rows_lds_bytes(li), S, D, t, li);
+        emit_kernel(e, dm == 2 ? k_tick_rows<true, 2> : (dm == 1 ? k_tick_rows<true, 1> : k_tick_rows<true, 0>), grid, block, rows_lds_bytes(li), S, D, t, li);
     } else {
-        emit_rows(e, dm == 2 ? k_tick_rows<false, 2> : (dm == 1 ? k_tick_rows<false, 1> : k_tick_rows<false, 0>), grid, block, rows_lds_bytes(lds_ints), S, D, t, lds_ints);
+        emit_kernel(e, dm == 2 ? k_tick_rows<false, 2> : (dm == 1 ? k_tick_rows<false, 1> : k_tick_rows<false, 0>), grid, block, rows_lds_bytes(lds_ints), S, D, t, lds_ints);
     }
 }
 
-// main kernel of a tick without neighbour search on the wide layout (the one bench.py brackets with events)
-void launch_tick_main(const Static &S, const State &D, int t, int lds_ints, hipStream_t st) {
-    if (S.fast_ok) {
-        Emit e; e.st = st;
-        emit_tick_rows(e, S, D, t, lds_ints, 0, 0);
-        return;
-    }
+// main kernel of a tick without neighbour search on the wide layout where the row-mapped kernel does not apply (!S.fast_ok)
+void launch_tick_generic(const Static &S, const State &D, int t, int lds_ints, hipStream_t st) {
     const int chunks = (S.R + 15) / 16;
     hipLaunchKernelGGL(k_tick<true>, dim3(S.C * chunks), dim3(256), (size_t)lds_ints * 4, st, S, D, t, lds_ints);
 }
@@ -1515,15 +1504,10 @@ void emit_hybrid_rows(const Emit &e, const Static &S0, const State &D, int t, in
     const dim3 grid(S.C * rchunks), block(ROWS_WAVES * WAVE);
     if (S.u8_ok) {
         const int li = min(lds_ints, (S.max_nc * S.max_nc + 15) / 16 * 4);
-        emit_rows(e, dm == 2 ? k_tick_rows<true, 2, true> : (dm == 1 ? k_tick_rows<true, 1, true> : k_tick_rows<true, 0, true>), grid, block, rows_lds_bytes(li), S, D, t, li);
+        emit_kernel(e, dm == 2 ? k_tick_rows<true, 2, true> : (dm == 1 ? k_tick_rows<true, 1, true> : k_tick_rows<true, 0, true>), grid, block, rows_lds_bytes(li), S, D, t, li);
     } else {
-        emit_rows(e, dm == 2 ? k_tick_rows<false, 2, true> : (dm == 1 ? k_tick_rows<false, 1, true> : k_tick_rows<false, 0, true>), grid, block, rows_lds_bytes(lds_ints), S, D, t, lds_ints);
+        emit_kernel(e, dm == 2 ? k_tick_rows<false, 2, true> : (dm == 1 ? k_tick_rows<false, 1, true> : k_tick_rows<false, 0, true>), grid, block, rows_lds_bytes(lds_ints), S, D, t, lds_ints);
     }
-}
-
-void launch_hybrid_rows(const Static &S, const State &D, int t, int lds_ints, hipStream_t st, int r_lo, int r_n) {
-    Emit e; e.st = st;
-    emit_hybrid_rows(e, S, D, t, lds_ints, r_lo, r_n);
 }
 
 void launch_dispatch(const Static &S, const State &D, int t, int ngroups, const int *grp_off, const int *a_replica,
@@ -1538,23 +1522,13 @@ void emit_dispatch_dense(const Emit &e, const Static &S0, const State &D, int t,
     Static S = S0;
     S.r_lo = r_lo;
     const dim3 grid(r_n > 0 ? r_n : S.R - r_lo), block(64);
-    if (!e.graph) { hipLaunchKernelGGL(k_dispatch_dense, grid, block, 0, e.st, S, D, t, K, actions, seq_base); return; }
-    State Dv = D;
-    void *args[6] = {&S, &Dv, &t, &K, &actions, &seq_base};
-    hipKernelNodeParams p{};
-    p.func = reinterpret_cast<void *>(k_dispatch_dense); p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = 0; p.kernelParams = args; p.extra = nullptr;
-    *e.err = hipGraphAddKernelNode(e.node, e.graph, e.deps, e.ndeps, &p);
+    emit_kernel(e, k_dispatch_dense, grid, block, 0, S, D, t, K, actions, seq_base);
 }
 void emit_pack_obs(const Emit &e, const Static &S0, const State &D, int t, int stepped, int planes, int *obs, int r_lo, int r_n) {
     Static S = S0;
     S.r_lo = r_lo;
     const dim3 grid(((r_n > 0 ? r_n : S.R - r_lo) + 15) / 16, (S.C + 15) / 16), block(256);
-    if (!e.graph) { hipLaunchKernelGGL(k_pack_obs, grid, block, 0, e.st, S, D, t, stepped, planes, obs); return; }
-    State Dv = D;
-    void *args[6] = {&S, &Dv, &t, &stepped, &planes, &obs};
-    hipKernelNodeParams p{};
-    p.func = reinterpret_cast<void *>(k_pack_obs); p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = 0; p.kernelParams = args; p.extra = nullptr;
-    *e.err = hipGraphAddKernelNode(e.node, e.graph, e.deps, e.ndeps, &p);
+    emit_kernel(e, k_pack_obs, grid, block, 0, S, D, t, stepped, planes, obs);
 }
 
 void launch_dispatch_dense(const Static &S, const State &D, int t, int K, const int *actions, int seq_base, hipStream_t st) {

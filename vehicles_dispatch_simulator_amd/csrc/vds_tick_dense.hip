@@ -29,6 +29,7 @@
 // Rows the tables cannot hold (> 128 / 256 entries, > 64 arrivals), rows with far arrivals and buckets with > 64 orders are
 // finished by the same wavefront with dense_bucket_slow (any size, straight from HBM).
 #include "vds_kernels_common.h"
+#include "vds_launch.h"
 #include <algorithm>
 
 namespace vds {
@@ -1406,26 +1407,12 @@ void emit_dense_flush(const Emit &e, const Static &S, const State &D, int r_lo, 
     if (r_n <= 0) r_n = S.R - r_lo;
     const long long nb = (long long)S.C * r_n;
     const dim3 grid((unsigned)((nb + 3) / 4)), block(256);
-    int *hdr = D.hdr; unsigned *idle = reinterpret_cast<unsigned *>(D.idle); unsigned short *stamp = D.stamp;
-    int R = S.R, C = S.C, cap = S.idle_cap;
-    if (!e.graph) { hipLaunchKernelGGL(k_dense_flush, grid, block, 0, e.st, hdr, idle, stamp, R, C, cap, r_lo, r_n); return; }
-    void *args[8] = {&hdr, &idle, &stamp, &R, &C, &cap, &r_lo, &r_n};
-    hipKernelNodeParams p{};
-    p.func = reinterpret_cast<void *>(k_dense_flush); p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = 0; p.kernelParams = args; p.extra = nullptr;
-    *e.err = hipGraphAddKernelNode(e.node, e.graph, e.deps, e.ndeps, &p);
+    emit_kernel(e, k_dense_flush, grid, block, 0, D.hdr, reinterpret_cast<unsigned *>(D.idle), D.stamp, S.R, S.C, S.idle_cap, r_lo, r_n);
 }
 
 // ---------------------------------------------------------------------------------------
 // launcher: the dense tick for the replicas [r_lo, r_lo + r_n) (r_lo a multiple of 16; r_n = 0: all), on a stream or as a kernel
 // node of an explicitly built hipGraph (vds_run's day graph)
-
-static void emit_dense(const Emit &e, void (*k)(DenseArgs, int), dim3 grid, dim3 block, size_t lds, DenseArgs P, int t) {
-    if (!e.graph) { hipLaunchKernelGGL(k, grid, block, lds, e.st, P, t); return; }
-    void *args[2] = {&P, &t};
-    hipKernelNodeParams p{};
-    p.func = reinterpret_cast<void *>(k); p.gridDim = grid; p.blockDim = block; p.sharedMemBytes = (unsigned)lds; p.kernelParams = args; p.extra = nullptr;
-    *e.err = hipGraphAddKernelNode(e.node, e.graph, e.deps, e.ndeps, &p);
-}
 
 // 256-entry tables: order days per replica, 16 lanes per replica, byte costs (see k_tick_dense)
 static bool dense_tab256(const Static &S) { return S.dense_lpr == 16 && S.blk8s != nullptr && S.dense_tab > 128; }
@@ -1433,11 +1420,11 @@ static bool dense_tab256(const Static &S) { return S.dense_lpr == 16 && S.blk8s 
 template <bool PULL>
 static void emit_dense_256(const Emit &e, const Static &S, const DenseArgs &P, int t, dim3 grid, size_t lds) {
     const dim3 block(DN_ROWS * 16);
-    if (S.n_days > 1 && S.chunk_days && S.row_gran == 8) { emit_dense(e, k_tick_dense<true, 1, 16, PULL, 256, 8>, grid, dim3(8 * 16), lds, P, t); return; }
-    if (S.n_days > 1 && S.chunk_days && S.row_gran == 4) { emit_dense(e, k_tick_dense<true, 1, 16, PULL, 256, 4>, grid, dim3(4 * 16), lds, P, t); return; }
-    if (S.n_days <= 1) emit_dense(e, k_tick_dense<true, 0, 16, PULL, 256>, grid, block, lds, P, t);
-    else if (S.chunk_days) emit_dense(e, k_tick_dense<true, 1, 16, PULL, 256>, grid, block, lds, P, t);
-    else emit_dense(e, k_tick_dense<true, 2, 16, PULL, 256>, grid, block, lds, P, t);
+    if (S.n_days > 1 && S.chunk_days && S.row_gran == 8) { emit_kernel(e, k_tick_dense<true, 1, 16, PULL, 256, 8>, grid, dim3(8 * 16), lds, P, t); return; }
+    if (S.n_days > 1 && S.chunk_days && S.row_gran == 4) { emit_kernel(e, k_tick_dense<true, 1, 16, PULL, 256, 4>, grid, dim3(4 * 16), lds, P, t); return; }
+    if (S.n_days <= 1) emit_kernel(e, k_tick_dense<true, 0, 16, PULL, 256>, grid, block, lds, P, t);
+    else if (S.chunk_days) emit_kernel(e, k_tick_dense<true, 1, 16, PULL, 256>, grid, block, lds, P, t);
+    else emit_kernel(e, k_tick_dense<true, 2, 16, PULL, 256>, grid, block, lds, P, t);
 }
 
 template <int LPR, bool PULL>
@@ -1445,17 +1432,17 @@ static void emit_dense_lpr(const Emit &e, const Static &S, const DenseArgs &P, i
     const int dm = S.n_days <= 1 ? 0 : (S.chunk_days ? 1 : 2);
     const dim3 block(DN_ROWS * LPR);
     if (LPR == 16 && dm == 1 && S.row_gran == 8) {      // day groups of eight replicas: 8-row workgroups
-        if (S.blk8s) emit_dense(e, k_tick_dense<true, 1, 16, PULL, DN_TAB, 8>, grid, dim3(8 * 16), lds, P, t);
-        else emit_dense(e, k_tick_dense<false, 1, 16, PULL, DN_TAB, 8>, grid, dim3(8 * 16), lds, P, t);
+        if (S.blk8s) emit_kernel(e, k_tick_dense<true, 1, 16, PULL, DN_TAB, 8>, grid, dim3(8 * 16), lds, P, t);
+        else emit_kernel(e, k_tick_dense<false, 1, 16, PULL, DN_TAB, 8>, grid, dim3(8 * 16), lds, P, t);
         return;
     }
     if (LPR == 16 && dm == 1 && S.row_gran == 4) {      // ... of four: one wavefront per workgroup
-        if (S.blk8s) emit_dense(e, k_tick_dense<true, 1, 16, PULL, DN_TAB, 4>, grid, dim3(4 * 16), lds, P, t);
-        else emit_dense(e, k_tick_dense<false, 1, 16, PULL, DN_TAB, 4>, grid, dim3(4 * 16), lds, P, t);
+        if (S.blk8s) emit_kernel(e, k_tick_dense<true, 1, 16, PULL, DN_TAB, 4>, grid, dim3(4 * 16), lds, P, t);
+        else emit_kernel(e, k_tick_dense<false, 1, 16, PULL, DN_TAB, 4>, grid, dim3(4 * 16), lds, P, t);
         return;
     }
-    if (S.blk8s) emit_dense(e, dm == 2 ? k_tick_dense<true, 2, LPR, PULL> : (dm ? k_tick_dense<true, 1, LPR, PULL> : k_tick_dense<true, 0, LPR, PULL>), grid, block, lds, P, t);
-    else emit_dense(e, dm == 2 ? k_tick_dense<false, 2, LPR, PULL> : (dm ? k_tick_dense<false, 1, LPR, PULL> : k_tick_dense<false, 0, LPR, PULL>), grid, block, lds, P, t);
+    if (S.blk8s) emit_kernel(e, dm == 2 ? k_tick_dense<true, 2, LPR, PULL> : (dm ? k_tick_dense<true, 1, LPR, PULL> : k_tick_dense<true, 0, LPR, PULL>), grid, block, lds, P, t);
+    else emit_kernel(e, dm == 2 ? k_tick_dense<false, 2, LPR, PULL> : (dm ? k_tick_dense<false, 1, LPR, PULL> : k_tick_dense<false, 0, LPR, PULL>), grid, block, lds, P, t);
 }
 
 // S.self_dev / S.state_dev: device-resident copies of S and D (kept current by vds_api.hip: dev_copy_sync) for the slow path
@@ -1495,8 +1482,8 @@ void emit_tick_dense_mixed(const Emit &e, const Static &S, const State &D, int t
     DenseArgs P = dense_args(S, D, 0, 0);
     P.bmap = bmap;
     const size_t lds = std::max(dense_lds(S, 32, DN_TAB), dense_lds(S, DN_ROWS, 256));
-    if (S.dense_st) emit_dense(e, k_tick_dense_mixed<true>, dim3(nblk), dim3(256), lds, P, t);
-    else emit_dense(e, k_tick_dense_mixed<false>, dim3(nblk), dim3(256), lds, P, t);
+    if (S.dense_st) emit_kernel(e, k_tick_dense_mixed<true>, dim3(nblk), dim3(256), lds, P, t);
+    else emit_kernel(e, k_tick_dense_mixed<false>, dim3(nblk), dim3(256), lds, P, t);
 }
 
 void emit_tick_dense(const Emit &e, const Static &S, const State &D, int t, int r_lo, int r_n) {
@@ -1512,14 +1499,14 @@ void emit_tick_dense(const Emit &e, const Static &S, const State &D, int t, int 
     const size_t lds = dense_lds(S, rows, t256 ? 256 : DN_TAB);
     if (S.dense_st) {
         // stamp form (neighbour search; vds_api.hip grants it for byte costs, one shared day, static arrival slots)
-        if (t256) emit_dense(e, k_tick_dense<true, 0, 16, true, 256, DN_ROWS, true>, grid, dim3(DN_ROWS * 16), lds, P, t);
-        else if (rows32) emit_dense(e, k_tick_dense<true, 0, 8, true, DN_TAB, 32, true>, grid, dim3(32 * 8), lds, P, t);
-        else if (S.dense_lpr == 8) emit_dense(e, k_tick_dense<true, 0, 8, true, DN_TAB, DN_ROWS, true>, grid, dim3(DN_ROWS * 8), lds, P, t);
-        else emit_dense(e, k_tick_dense<true, 0, 16, true, DN_TAB, DN_ROWS, true>, grid, dim3(DN_ROWS * 16), lds, P, t);
+        if (t256) emit_kernel(e, k_tick_dense<true, 0, 16, true, 256, DN_ROWS, true>, grid, dim3(DN_ROWS * 16), lds, P, t);
+        else if (rows32) emit_kernel(e, k_tick_dense<true, 0, 8, true, DN_TAB, 32, true>, grid, dim3(32 * 8), lds, P, t);
+        else if (S.dense_lpr == 8) emit_kernel(e, k_tick_dense<true, 0, 8, true, DN_TAB, DN_ROWS, true>, grid, dim3(DN_ROWS * 8), lds, P, t);
+        else emit_kernel(e, k_tick_dense<true, 0, 16, true, DN_TAB, DN_ROWS, true>, grid, dim3(DN_ROWS * 16), lds, P, t);
         return;
     }
     if (rows32) {
-        emit_dense(e, k_tick_dense<true, 0, 8, true, DN_TAB, 32>, grid, dim3(32 * 8), lds, P, t);
+        emit_kernel(e, k_tick_dense<true, 0, 8, true, DN_TAB, 32>, grid, dim3(32 * 8), lds, P, t);
         return;
     }
     if (t256) {

@@ -258,8 +258,9 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_run_hooked_invalidate(self._h))
 
     def set_run_groups(self, groups: int = 0, stagger: int = -1):
-        """Scheduling of ``run`` (``vds_set_run_groups``): the replicas as ``groups`` independent chains of launches (parallel
-        branches of the day graph); results do not depend on it.  ``groups <= 0`` / ``stagger < 0``: library default."""
+        """Scheduling of ``run`` / ``run_hooked`` (``vds_set_run_groups``): the replicas as ``groups`` groups with launches of their
+        own, one after another in the day graph; results do not depend on it.  ``groups <= 0``: library default (one).
+        ``stagger`` is accepted (up to 2) and has no effect."""
         self._chk(self._lib.vds_set_run_groups(self._h, int(groups), int(stagger)))
 
     def tick_forms(self) -> np.ndarray:
