@@ -11,10 +11,52 @@ from oracle.oracle import Oracle
 from vehicles_dispatch_simulator_amd import synth
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+DEFAULT_REJECT_THRESHOLD = 600_000_000_000      # raw integer of the reference's PICKUPTIMEWINDOW
 
 
 def golden_names(prefix="tiny_"):
     return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, prefix + "*.npz")))
+
+
+_FUZZ_INDEX = None
+
+
+def _fuzz_index():
+    """case name -> pack file of the fuzz corpus (tests/golden/make_fuzz_golden.py: a few cases per file, keys "<case>/<array>")."""
+    global _FUZZ_INDEX
+    if _FUZZ_INDEX is None:
+        _FUZZ_INDEX = {}
+        for p in sorted(glob.glob(os.path.join(GOLDEN_DIR, "fuzzpack_*.npz"))):
+            with np.load(p) as z:
+                for k in z.files:
+                    _FUZZ_INDEX[k.split("/")[0]] = p
+    return _FUZZ_INDEX
+
+
+def fuzz_names():
+    return sorted(_fuzz_index())
+
+
+def forget_fuzz_index():
+    """The pack files changed (the generator rewrote them): list them again on the next use."""
+    global _FUZZ_INDEX
+    _FUZZ_INDEX = None
+
+
+def load_fuzz(name):
+    """One case of the fuzz corpus in the form of a tiny fixture (integer arrays were stored in their narrowest type)."""
+    g = {}
+    with np.load(_fuzz_index()[name]) as z:
+        for k in z.files:
+            if k.startswith(name + "/"):
+                a = z[k]
+                g[k[len(name) + 1:]] = a.astype(np.int32) if a.dtype == np.int16 else a
+    return g
+
+
+def live_window(g):
+    """The fixture's raw pickup window can reject a vehicle that was found (below the reference's default, which no cost reaches)."""
+    return engine_settings(g)["reject_threshold"] < DEFAULT_REJECT_THRESHOLD
 
 
 def load_golden(name):
@@ -22,6 +64,8 @@ def load_golden(name):
 
     Real-shape fixtures do not store the city: it is regenerated from the recorded seed
     (the generator asserted equality with what the reference loaded)."""
+    if name.startswith("fuzz_"):
+        return load_fuzz(name)
     g = dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz")))
     if "cost" not in g and str(g["city_mode"]) == "shipped":
         # the reference's shipped road graph and clustering (labels / neighbour lists are in the fixture);
@@ -50,7 +94,7 @@ def make_oracle(g) -> Oracle:
 def engine_settings(g):
     """tick length / raw pickup window of a fixture (older fixtures: the reference's defaults)."""
     return dict(tick_minutes=int(g["tick_minutes"]) if "tick_minutes" in g else 10,
-                reject_threshold=int(g["reject_threshold"]) if "reject_threshold" in g else 600_000_000_000)
+                reject_threshold=int(g["reject_threshold"]) if "reject_threshold" in g else DEFAULT_REJECT_THRESHOLD)
 
 
 def dispatch_by_tick(g):
@@ -59,3 +103,91 @@ def dispatch_by_tick(g):
     for row in log:
         out.setdefault(int(row[0]), []).append(row)
     return out
+
+
+def recorded_day_facts(g):
+    """What a recorded day exercised, derived from the reference's record alone (no oracle): the number of orders served by a
+    vehicle from another cluster than the pickup's, of orders rejected although the pickup's own cluster held an idle vehicle
+    (only the pickup window rejects those) and of orders rejected with the own cluster empty of idle vehicles.
+
+    Orders are processed in id order, ``t_order_num`` says in which tick; a vehicle stands where its last trip (order or
+    dispatch) ended, and the idle count a rejected order saw in its own cluster is the post-match count of the tick plus the
+    vehicles that later orders of the tick took from that cluster."""
+    n2c, cost = g["node2cluster"], g["cost"]
+    loc = g["veh_node"].astype(np.int64).copy()
+    disp = dispatch_by_tick(g)
+    facts = dict(cross=0, window_rejects=0, empty_rejects=0)
+    first = 0
+    for t in range(int(g["n_ticks"])):
+        last = int(g["t_order_num"][t])
+        src = {}
+        for o in range(first, last):
+            if g["o_status"][o] == 1:
+                v, p = int(g["o_vehicle"][o]), int(g["o_pickup"][o])
+                assert g["o_wait"][o] == cost[p, loc[v]], (t, o)
+                src[o] = int(n2c[loc[v]])
+                facts["cross"] += src[o] != n2c[p]
+                loc[v] = g["o_delivery"][o]
+        taken = np.zeros(int(g["C"]), dtype=np.int64)
+        for o in range(last - 1, first - 1, -1):
+            pc = n2c[g["o_pickup"][o]]
+            if g["o_status"][o] == 1:
+                taken[src[o]] += 1
+            elif g["t_idle_post"][t][pc] + taken[pc] > 0:
+                facts["window_rejects"] += 1
+            else:
+                facts["empty_rejects"] += 1
+        for row in disp.get(t, ()):
+            loc[int(row[1])] = int(row[4])
+        first = last
+    assert first == int(g["order_num"]) and facts["window_rejects"] + facts["empty_rejects"] == int(g["reject_num"])
+    assert facts["window_rejects"] == 0 or live_window(g)
+    return facts
+
+
+def clusters_without_nodes(g):
+    return int((np.bincount(g["node2cluster"][g["node2cluster"] >= 0], minlength=int(g["C"])) == 0).sum())
+
+
+def fuzz_coverage_gaps(cases):
+    """The coverage conditions of the fuzz corpus (tests/golden/make_fuzz_golden.py) that ``cases`` ({name: fixture}) leave
+    unmet, as a list of sentences; asserted empty by the generator and by tests/test_oracle_fuzz_golden.py."""
+    rows = []
+    for name, g in cases.items():
+        f = recorded_day_facts(g)
+        nbr = bool(g["neighbor_can_server"])
+        integral = bool(g["cost_is_integral"])
+        rows.append(dict(f, name=name, depth=int(g["depth_limit"]), nbr=nbr, tick=int(g["tick_minutes"]),
+                         window=int(g["reject_threshold"]) if live_window(g) else None, V=int(g["V"]), C=int(g["C"]),
+                         dispatch=int(g["dispatch_num"]) > 0, negative=bool((g["cost"] < 0).any()), frac=not integral,
+                         div7=str(g["style"]) == "div7", no_node=clusters_without_nodes(g),
+                         outside=bool((g["node2cluster"] < 0).any())))
+    gaps = []
+
+    def need(what, pred, n=1):
+        if sum(1 for r in rows if pred(r)) < n:
+            gaps.append(what)
+
+    for d in range(-1, 5):
+        need("depth %d three times with neighbour search" % d, lambda r: r["nbr"] and r["depth"] == d, 3)
+        if d >= 1:
+            need("depth %d: an order served from another cluster" % d, lambda r: r["nbr"] and r["depth"] == d and r["cross"] > 0)
+    need("depth -1 with neighbour search: a reject with the own cluster empty", lambda r: r["nbr"] and r["depth"] == -1 and r["empty_rejects"] > 0)
+    for t in (10, 5, 15, 7, 3):
+        need("tick %d three times" % t, lambda r: r["tick"] == t, 3)
+    for w in (None, 40, 8, 0):
+        need("window %s three times" % w, lambda r: r["window"] == w, 3)
+        if w is not None:
+            need("window %d: rejects caused by the window" % w, lambda r: r["window"] == w and r["window_rejects"] > 0)
+            need("window %d with neighbour search at depth >= 1" % w, lambda r: r["window"] == w and r["nbr"] and r["depth"] >= 1)
+    for style in ("negative", "div7", "frac"):
+        need("%s costs three times" % style, lambda r: r[style], 3)
+        need("%s costs with dispatch" % style, lambda r: r[style] and r["dispatch"])
+    need("V = 0", lambda r: r["V"] == 0)
+    need("0 < V <= 4", lambda r: 0 < r["V"] <= 4)
+    need("C = 48 with clusters that own no node", lambda r: r["C"] == 48 and r["no_node"] > 0)
+    need("dispatch with a tick other than 10", lambda r: r["dispatch"] and r["tick"] != 10)
+    need("dispatch with a live window", lambda r: r["dispatch"] and r["window"] is not None)
+    need("dispatch with depth >= 2", lambda r: r["dispatch"] and r["nbr"] and r["depth"] >= 2)
+    need("nodes outside every cluster with depth >= 1 and a live window", lambda r: r["outside"] and r["nbr"] and r["depth"] >= 1 and r["window"] is not None)
+    return gaps

@@ -7,7 +7,7 @@ import random
 import numpy as np
 import pytest
 
-from helpers import dispatch_by_tick, engine_settings, golden_names, load_golden, make_oracle
+from helpers import dispatch_by_tick, engine_settings, golden_names, live_window, load_golden, make_oracle
 from oracle.oracle import Oracle
 from vehicles_dispatch_simulator_amd import BatchedDispatchEnv, synth
 from vehicles_dispatch_simulator_amd.env import neighbors_to_csr
@@ -222,9 +222,9 @@ def _applies(name, mode, every_pair=False):
     if name not in ALL_MODES_ON and mode not in BASE_MODES and not every_pair:
         return False
     if mode.startswith("dense_ring") or mode.startswith("rows"):
-        return not searching and "window" not in name
+        return not searching and not live_window(g)
     if mode.startswith("dense"):       # (neighbour search runs on the dense layout too: stamp form; a live pickup window keeps the wide layout)
-        return "window" not in name
+        return not live_window(g)
     if mode.startswith("dfs_"):
         return searching
     return True

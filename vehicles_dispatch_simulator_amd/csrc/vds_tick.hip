@@ -1382,7 +1382,8 @@ __global__ __launch_bounds__(64) void k_dispatch_dense(Static S, State D, int t,
         wave_fence();
         while (todo) {
             const int leader = __ffsll((long long)todo) - 1;
-            const unsigned long long grp = ((unsigned long long)__builtin_amdgcn_readlane((int)(same & 0xFFFFFFFFu), leader)) |
+            // (both halves through unsigned: a set bit 31 - slot 31 in the leader's group - must not sign-extend over slots 32-63)
+            const unsigned long long grp = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(same & 0xFFFFFFFFu), leader)) |
                                            ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(same >> 32), leader) << 32);
             const int c = rdlane(cl, leader);
             const int mc = rdlane(m, leader);
