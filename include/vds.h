@@ -334,6 +334,28 @@ int vds_counters_device(vds_handle *h, void **dev_ptr);
 int vds_outcomes_device(vds_handle *h, void **dev_ptr);
 int vds_read_outcomes(vds_handle *h, int64_t *served, int64_t *rejected, int64_t *wait_sum, int64_t *value_sum);
 
+/* The heads of every idle list - what a DispatchFunction sees when it walks `for vehicle in cluster.IdleVehicles` (simulator.py:893-898;
+ * objects.py: Cluster.IdleVehicles, Vehicle.ID, Vehicle.LocationNode): the first L entries of Clusters[c].IdleVehicles of every
+ * replica as two int32 planes [2][R][C][L], replicas in the caller's order:
+ *   0 veh    Vehicle.ID of the vehicle at list position p
+ *   1 node   its LocationNode, a global node id
+ * both -1 for p >= len(IdleVehicles).  Position p IS the idle_pos of vds_apply_dispatch / _ex / _device.  L in 1 .. VDS_IDLE_HEADS_MAX
+ * (VDS_EINVAL otherwise); VDS_EINVAL before vds_reset.  A replica whose order day is over reports its standing lists.
+ * vds_idle_heads_device refreshes the block asynchronously on the handle's stream from the lists as they stand - after a reset, a
+ * step, a dispatch of the same slot, a run - and returns its device address: one block per handle for one L at a time, made on
+ * the first call, fixed until the tables are re-made (as for vds_outcomes_device) or another L is asked for (which makes it again).
+ * No tick, vds_run or vds_run_hooked computes it unless vds_run_hooked_idle_heads switched it on.
+ * vds_read_idle_heads: the same, copied to the host (synchronous), each [R*C*L] replica-major; either pointer may be NULL. */
+#define VDS_IDLE_HEADS_MAX 64
+int vds_idle_heads_device(vds_handle *h, int32_t L, void **dev_ptr);
+int vds_read_idle_heads(vds_handle *h, int32_t L, int32_t *veh, int32_t *node);
+
+/* Sticky switch of vds_run_hooked: L > 0 - every slot of the calls that follow refreshes the block of vds_idle_heads_device(L)
+ * behind the slot's tick and observation planes and before the policy node, so a captured policy reads the heads of the slot (get
+ * the address from vds_idle_heads_device(L) before capturing: it is the one the day uses); 0 - off, the default: nothing is
+ * launched.  L outside 0 .. VDS_IDLE_HEADS_MAX: VDS_EINVAL.  A parameter of its own, not a bit of `planes` (which stays 0 .. 63). */
+int vds_run_hooked_idle_heads(vds_handle *h, int32_t L);
+
 /* As vds_reduce_counters, delivering the int64 [VDS_NUM_COUNTERS] totals of this handle's
  * replicas (raw device sums; VALUE_SUM = matched orders only) into caller-owned DEVICE memory,
  * asynchronously on the handle's stream - the send buffer of the cross-GPU RCCL all-reduce. */

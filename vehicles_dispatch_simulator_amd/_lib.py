@@ -78,6 +78,9 @@ SYMBOLS = {
     "vds_counters_device": (C.c_int, [_VP, C.POINTER(_VP)]),
     "vds_outcomes_device": (C.c_int, [_VP, C.POINTER(_VP)]),
     "vds_read_outcomes": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "vds_idle_heads_device": (C.c_int, [_VP, _I32, C.POINTER(_VP)]),
+    "vds_read_idle_heads": (C.c_int, [_VP, _I32, _VP, _VP]),
+    "vds_run_hooked_idle_heads": (C.c_int, [_VP, _I32]),
     "vds_read_counters": (C.c_int, [_VP, _VP]),
     "vds_reduce_counters": (C.c_int, [_VP, _VP, C.POINTER(_VP)]),
     "vds_reduce_counters_into": (C.c_int, [_VP, _VP]),

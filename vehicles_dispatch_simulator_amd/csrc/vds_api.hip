@@ -198,6 +198,7 @@ struct vds_handle {
     unsigned long long *d_bad = nullptr;     // replace d_veh_node (index of the first node outside every cluster, ~0 if none)
     int *d_obs = nullptr;
     long long *d_outc = nullptr;             // vds_outcomes_device: int64 [4][R_ext][C], made on the first request (in state_allocs)
+    int *d_heads = nullptr; int heads_L = 0; // vds_idle_heads_device: int32 [2][R_ext][C][heads_L], made on the first request (in state_allocs)
     long long *d_cnt_per = nullptr, *d_cnt_tot = nullptr;
     int *d_actions = nullptr;
     size_t actions_cap = 0;
@@ -243,6 +244,8 @@ struct vds_handle {
     int hook_t0 = -1, hook_n = 0, hook_G = 1, hook_planes = 0, hook_K = 0;
     unsigned hook_gen = 0;
     const long long *hook_outc = nullptr;
+    int hooked_heads_L = 0;                  // vds_run_hooked_idle_heads: > 0 - every slot of vds_run_hooked refreshes the heads block (sticky)
+    const int *hook_heads = nullptr; int hook_heads_L = 0;   // ... and what the graph at hand was built with
     const void *hook_actions = nullptr;
     void *hook_policy = nullptr;
     hipStream_t hook_stream = nullptr;
@@ -987,6 +990,7 @@ static int alloc_state(vds_handle *h, int O) {
     for (void *p : h->state_allocs) dev_free(p);
     h->state_allocs.clear();
     h->d_outc = nullptr;                                 // (the outcome block lived there: made again on the next request)
+    h->d_heads = nullptr; h->heads_L = 0;                // (and the idle-heads block)
     S.idle_cap = idle_cap; S.fl_cap = far_cap; S.in_cap = far_cap; S.H = H; S.ring_cap = ring_cap;
     const size_t B = (size_t)C * R;
     h->alloc_dense = S.dense; h->alloc_st = S.dense_st;
@@ -2235,6 +2239,7 @@ int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger) {
 // request only, see below) are launches of that chain, and the policy node, which sees all replicas, comes behind the last group's
 // planes and before the first group's dispatch.
 static int ensure_outcomes(vds_handle *h);
+static int ensure_idle_heads(vds_handle *h, int L);
 
 static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
     if (policy_graph && h->hook_policy_inst != policy_graph) {
@@ -2247,6 +2252,7 @@ static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int3
         if (rc) return rc;
         if ((planes & 31) && (rc = vds_obs_device_planes(h, planes & 31, nullptr))) return rc;
         if ((planes & VDS_PLANE_OUTCOMES) && (rc = vds_outcomes_device(h, nullptr))) return rc;
+        if (h->hooked_heads_L > 0 && (rc = vds_idle_heads_device(h, h->hooked_heads_L, nullptr))) return rc;
         if (policy_graph) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
         if (K > 0 && dev_actions && (rc = vds_apply_dispatch_device(h, K, dev_actions))) return rc;
         if ((rc = vds_advance(h))) return rc;
@@ -2263,6 +2269,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     if (n_ticks == 0) return VDS_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (planes & VDS_PLANE_OUTCOMES) { const int rco = ensure_outcomes(h); if (rco) return rco; }
+    const int HL = h->hooked_heads_L;
+    if (HL > 0) { const int rch = ensure_idle_heads(h, HL); if (rch) return rch; }
     const bool groupable = run_groups_hybrid(h) || run_groups_plain(h);
     if (!run_graph_on(h) || h->profiling || !groupable) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
     { const int rcs = dev_copy_sync(h); if (rcs) return rcs; }
@@ -2273,7 +2281,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     (void)run_group_count(h);
     const int G = h->run_groups > 0 ? std::min(run_group_count(h), RUN_GROUPS_MAX) : 1;
     const bool same = h->hook_exec && h->hook_gen == h->tables_gen && h->hook_t0 == h->t && h->hook_n == n_ticks && h->hook_G == G && h->hook_planes == planes && h->hook_K == K &&
-                      h->hook_actions == dev_actions && h->hook_policy == policy_graph && h->hook_stream == h->stream && h->hook_outc == h->d_outc;
+                      h->hook_actions == dev_actions && h->hook_policy == policy_graph && h->hook_stream == h->stream && h->hook_outc == h->d_outc &&
+                      h->hook_heads == (HL > 0 ? h->d_heads : nullptr) && h->hook_heads_L == HL;
     if (!same) {
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
@@ -2287,6 +2296,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                 if (planes & 31) c.add(emit_pack_obs, h->S, h->D, t, 1, planes & 31, h->d_obs, r.lo, r.n);
                 // the slot's per-cluster order outcomes, behind the group's last tick launch
                 if (planes & VDS_PLANE_OUTCOMES) c.add(emit_slot_outcomes, h->S, h->D, t, 1, h->d_outc, r.lo, r.n);
+                // the heads of the group's idle lists as the tick left them (vds_run_hooked_idle_heads)
+                if (HL > 0) c.add(emit_idle_heads, h->S, h->D, HL, h->d_heads, r.lo, r.n);
             }
             if (policy_graph) {
                 // (the child graph between two EMPTY nodes: with several parents / several children attached to the child-graph node
@@ -2305,11 +2316,12 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
             (void)hipGetLastError();
             return fail(h, VDS_EHIP, "vds_run_hooked: building the day graph failed: %s", hipGetErrorString(c.err));
         }
-        const bool same_shape = h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) &&
+        const bool same_shape = h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) && (h->hook_heads_L > 0) == (HL > 0) &&
                                 (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr);
         if (!install_graph(h, drop_hook_graph, &h->hook_exec, h->hook_stream, same_shape, g)) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
         h->hook_t0 = h->t; h->hook_n = n_ticks; h->hook_G = G; h->hook_planes = planes; h->hook_K = K; h->hook_actions = dev_actions;
         h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen; h->hook_outc = h->d_outc;
+        h->hook_heads = HL > 0 ? h->d_heads : nullptr; h->hook_heads_L = HL;
     }
     HIPCHK(h, hipGraphLaunch(h->hook_exec, h->stream));
     h->t += n_ticks;
@@ -2558,6 +2570,65 @@ static int read_outcomes_impl(vds_handle *h, int64_t *served, int64_t *rejected,
 
 int vds_read_outcomes(vds_handle *h, int64_t *served, int64_t *rejected, int64_t *wait_sum, int64_t *value_sum) {
     return guarded(h, "vds_read_outcomes", [&] { return read_outcomes_impl(h, served, rejected, wait_sum, value_sum); });
+}
+
+// The first L entries of every idle list (Cluster.IdleVehicles as DispatchFunction walks it, :893-898; objects.py: Vehicle.ID,
+// Vehicle.LocationNode): k_idle_heads into the int32 [2][R_ext][C][L] block, made on the first request for this L (it lives with the
+// state tables: re-made when they are, and when another L is asked for).
+static int ensure_idle_heads(vds_handle *h, int L) {
+    if (h->d_heads && h->heads_L == L) return VDS_OK;
+    if (h->d_heads) {                                    // another L: the block is made again (work that reads the old one may be in flight)
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        auto &v = h->state_allocs;
+        v.erase(std::remove(v.begin(), v.end(), (void *)h->d_heads), v.end());
+        dev_free(h->d_heads);
+        h->d_heads = nullptr; h->heads_L = 0;
+    }
+    struct Sink { vds_handle *h; std::vector<void *> *old; ~Sink() { h->alloc_sink = old; } } sink{h, h->alloc_sink};
+    h->alloc_sink = &h->state_allocs;
+    const size_t n = 2 * (size_t)h->R_ext * h->S.C * L;
+    const int rc = dev_alloc(h, &h->d_heads, n);
+    if (rc) { h->d_heads = nullptr; return rc; }
+    h->heads_L = L;
+    HIPCHK(h, hipMemsetAsync(h->d_heads, 0xFF, n * sizeof(int), h->stream));      // (-1: empty lists until the first refresh)
+    return VDS_OK;
+}
+
+static int idle_heads_device_impl(vds_handle *h, int32_t L, void **dev_ptr) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_idle_heads_device: call vds_reset first");
+    if (L < 1 || L > VDS_IDLE_HEADS_MAX) return fail(h, VDS_EINVAL, "vds_idle_heads_device: L = %d is outside 1 .. %d list positions", L, VDS_IDLE_HEADS_MAX);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int rc = ensure_idle_heads(h, L);
+    if (rc) return rc;
+    launch_idle_heads(h->S, h->D, L, h->d_heads, h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (dev_ptr) *dev_ptr = h->d_heads;
+    return VDS_OK;
+}
+
+int vds_idle_heads_device(vds_handle *h, int32_t L, void **dev_ptr) {
+    return guarded(h, "vds_idle_heads_device", [&] { return idle_heads_device_impl(h, L, dev_ptr); });
+}
+
+static int read_idle_heads_impl(vds_handle *h, int32_t L, int32_t *veh, int32_t *node) {
+    const int rc = idle_heads_device_impl(h, L, nullptr);
+    if (rc) return rc;
+    const size_t RCL = (size_t)h->R_ext * h->S.C * L;
+    int32_t *dst[2] = {veh, node};
+    for (int k = 0; k < 2; ++k)
+        if (dst[k]) HIPCHK(h, hipMemcpyAsync(dst[k], h->d_heads + k * RCL, RCL * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return vds_sync(h);
+}
+
+int vds_read_idle_heads(vds_handle *h, int32_t L, int32_t *veh, int32_t *node) {
+    return guarded(h, "vds_read_idle_heads", [&] { return read_idle_heads_impl(h, L, veh, node); });
+}
+
+int vds_run_hooked_idle_heads(vds_handle *h, int32_t L) {
+    if (!h) return VDS_EINVAL;
+    if (L < 0 || L > VDS_IDLE_HEADS_MAX) return fail(h, VDS_EINVAL, "vds_run_hooked_idle_heads: L = %d is outside 0 (off) .. %d list positions", L, VDS_IDLE_HEADS_MAX);
+    h->hooked_heads_L = L;
+    return VDS_OK;
 }
 
 static int read_counters_impl(vds_handle *h, int64_t *out) {

@@ -52,4 +52,7 @@ void launch_start_nodes_check(const int *veh_node, int R, int N, int V, int C, c
 // ---- vds_outcomes.hip
 void emit_slot_outcomes(const Emit &e, const Static &S, const State &D, int t, int stepped, long long *oc, int r_lo, int r_n);
 void launch_slot_outcomes(const Static &S, const State &D, int t, int stepped, long long *oc, hipStream_t st);
+// ---- vds_idle_heads.hip
+void emit_idle_heads(const Emit &e, const Static &S, const State &D, int L, int *heads, int r_lo, int r_n);
+void launch_idle_heads(const Static &S, const State &D, int L, int *heads, hipStream_t st);
 }  // namespace vds

@@ -231,10 +231,11 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_run(self._h, int(n_ticks)))
 
     def run_hooked(self, n_ticks: int, actions=None, policy_graph=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False,
-                   outcomes=False):
+                   outcomes=False, idle_heads=0):
         """``n_ticks`` slots of ``SimCity`` WITH the dispatch hook on the device as one graph launch (``vds_run_hooked``): per slot
         step -> the named observation planes into the block ``obs_torch`` returns (``outcomes=True``: also the slot's per-cluster
-        order outcomes into the block ``outcomes_torch`` returns) -> ``policy_graph`` -> ``actions`` applied ->
+        order outcomes into the block ``outcomes_torch`` returns; ``idle_heads=L``: also the first ``L`` entries of every idle list
+        into the block ``idle_heads_torch(L)`` returns - ``0`` switches that off again) -> ``policy_graph`` -> ``actions`` applied ->
         advance.  ``actions``: the contiguous int32 CUDA tensor ``[R, K, 3]`` the policy writes (``None``: no dispatch).
         ``policy_graph``: a ``torch.cuda.CUDAGraph`` captured with ``keep_graph=True`` (its ``raw_cuda_graph()`` is embedded), or a
         raw ``hipGraph_t`` as an integer, or ``None`` (the tensor is applied as it stands)."""
@@ -250,6 +251,7 @@ class BatchedDispatchEnv:
         raw = None
         if policy_graph is not None:
             raw = policy_graph if isinstance(policy_graph, int) else int(policy_graph.raw_cuda_graph())
+        self._chk(self._lib.vds_run_hooked_idle_heads(self._h, int(idle_heads)))
         self._chk(self._lib.vds_run_hooked(self._h, int(n_ticks), planes, K, ptr, C.c_void_p(raw) if raw is not None else None))
 
     def run_hooked_invalidate(self):
@@ -416,6 +418,34 @@ class BatchedDispatchEnv:
         arrs = [np.empty((self.R, self.C), dtype=np.int64) for _ in OUTCOME_NAMES]
         self._chk(self._lib.vds_read_outcomes(self._h, *[_p(a) for a in arrs]))
         return dict(zip(OUTCOME_NAMES, arrs))
+
+    def idle_heads_device_ptr(self, L: int) -> int:
+        """Device pointer of the int32 ``[2][R][C][L]`` block of idle-list heads, refreshed from the lists as they stand
+        (``vds_idle_heads_device``); fixed for one ``L`` until the state tables are re-made."""
+        p = C.c_void_p()
+        self._chk(self._lib.vds_idle_heads_device(self._h, int(L), C.byref(p)))
+        return p.value
+
+    def idle_heads_torch(self, L: int):
+        """The first ``L`` (1 .. 64) entries of ``Clusters[c].IdleVehicles`` of every replica as a zero-copy ``torch`` int32 tensor
+        ``[2, R, C, L]`` on the GPU: plane 0 ``Vehicle.ID``, plane 1 ``Vehicle.LocationNode`` (global node id), ``-1`` past the end of a
+        list.  The last index is the ``idle_pos`` of ``apply_dispatch*`` (``simulator.py:893-898``).  Refreshed by this call; aliases
+        library memory, overwritten by the next heads call or by ``run_hooked(idle_heads=L)``."""
+        import torch
+
+        class _Block:
+            pass
+
+        blk = _Block()
+        blk.__cuda_array_interface__ = {"shape": (2, self.R, self.C, int(L)), "typestr": "<i4", "data": (self.idle_heads_device_ptr(L), False),
+                                        "version": 2, "strides": None}
+        return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+
+    def idle_heads(self, L: int) -> Dict[str, np.ndarray]:
+        """``idle_heads_torch`` copied to the host: ``{veh, node}``, each int32 ``[R, C, L]``."""
+        arrs = [np.empty((self.R, self.C, max(int(L), 0)), dtype=np.int32) for _ in range(2)]
+        self._chk(self._lib.vds_read_idle_heads(self._h, int(L), *[_p(a) for a in arrs]))
+        return dict(zip(("veh", "node"), arrs))
 
     def counters(self) -> np.ndarray:
         out = np.zeros((self.R, _lib.NUM_COUNTERS), dtype=np.int64)

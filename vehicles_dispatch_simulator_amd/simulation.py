@@ -30,7 +30,11 @@ What a maintainer should know (also in INTEGRATION.md):
     (:1048-1091) - is ONE graph launch (``vds_run_hooked``); see ``BatchedPolicy``;
   * ``BatchedOutcomes=True`` (with ``BatchedHooks=True``): ``self.BatchedOutcomes`` holds how each cluster's orders fared in the
     slot - ``served`` / ``rejected`` / ``wait_sum`` / ``value_sum`` over ``Cluster.Orders`` (:919-1013), CUDA int64 tensors
-    ``[Replicas, clusters]`` - refreshed every slot before ``RewardFunction``; ``BatchedPolicy`` receives the same four keys.
+    ``[Replicas, clusters]`` - refreshed every slot before ``RewardFunction``; ``BatchedPolicy`` receives the same four keys;
+  * ``BatchedIdleHeads=L`` (1 .. 64, with ``BatchedHooks=True``): ``self.BatchedObs["idle_veh"]`` / ``["idle_node"]`` hold the first
+    ``L`` entries of every ``Cluster.IdleVehicles`` (:893-898) - ``Vehicle.ID`` and ``Vehicle.LocationNode``, ``-1`` past the end of a
+    list - as CUDA int32 tensors ``[Replicas, clusters, L]``, refreshed every slot before ``RewardFunction``; the last index is the
+    ``idle_pos`` of an action.  ``BatchedPolicy`` receives the same two keys.
 """
 from __future__ import annotations
 
@@ -82,7 +86,7 @@ class Simulation(object):
     def __init__(self, ClusterMode, DemandPredictionMode, DispatchMode, VehiclesNumber, TimePeriods, LocalRegionBound,
                  SideLengthMeter, VehiclesServiceMeter, NeighborCanServer, FocusOnLocalRegion,
                  Replicas=1, Replica=0, Device=0, VehicleSeed=None, DataDir=None, Quiet=False, BatchedHooks=False, BatchedOutcomes=False,
-                 **device_kwargs):
+                 BatchedIdleHeads=0, **device_kwargs):
         # components (simulator.py:44-45)
         self.DispatchModule = None
         self.DemandPredictorModule = None
@@ -138,6 +142,9 @@ class Simulation(object):
             raise Exception("BatchedOutcomes needs BatchedHooks=True (the planes are device tensors over all Replicas)")
         self._outcomes_on = bool(BatchedOutcomes)
         self.BatchedOutcomes = None         # BatchedOutcomes=True: {served, rejected, wait_sum, value_sum} of the slot, CUDA int64 [Replicas, clusters]
+        if BatchedIdleHeads and not self.BatchedHooks:
+            raise Exception("BatchedIdleHeads needs BatchedHooks=True (the planes are device tensors over all Replicas)")
+        self._idle_heads_L = int(BatchedIdleHeads)      # > 0: BatchedObs carries idle_veh / idle_node, CUDA int32 [Replicas, clusters, L]
         if self.BatchedHooks and "stream" not in device_kwargs:
             import torch          # the policy's tensors and the engine's launches share torch's current stream
             cs = torch.cuda.current_stream(int(Device)).cuda_stream
@@ -623,7 +630,40 @@ class Simulation(object):
         if self._outcomes_on:                           # (the outcome block: fixed address, rewritten by every slot of the day graph)
             obs.update(self._outcome_views())
             planes = dict(planes, outcomes=True)
+        if self._idle_heads_L:                          # (the heads block: likewise)
+            obs.update(self._idle_head_views())
+            planes = dict(planes, idle_heads=self._idle_heads_L)
         return obs, planes
+
+    def _idle_head_views(self):
+        """``{"idle_veh", "idle_node"}`` of the heads block as it stands now (refreshed by this call).  The device numbers vehicles by their
+        position in ``self.Vehicles``; where ``Vehicle.ID`` (the driver id) is another number, ``idle_veh`` is a tensor of its own that
+        ``_map_idle_ids`` fills from the block - at a fixed address, so a captured policy may read it."""
+        import torch
+        blk = self.env.idle_heads_torch(self._idle_heads_L)
+        st = getattr(self, "_idle_ids_state", None)
+        if st is None or st["env"] is not self.env:
+            ids = np.asarray([v.ID for v in self.Vehicles])
+            if ids.dtype.kind not in "iu" or (ids.size and (ids.min() < 0 or ids.max() >= 2 ** 31)):
+                raise Exception("BatchedIdleHeads: Vehicle.ID must be a non-negative int32 to live in a device tensor (the driver ids of this data set are %s)" % ids.dtype)
+            table = None if np.array_equal(ids, np.arange(ids.size)) else torch.from_numpy(ids.astype(np.int32)).to(blk.device)
+            st = self._idle_ids_state = dict(env=self.env, table=table, out=None)
+        if st["table"] is None:
+            return {"idle_veh": blk[0], "idle_node": blk[1]}
+        if st["out"] is None or st["out"].shape != blk[0].shape:
+            st["out"] = torch.empty_like(blk[0])
+        st["blk"] = blk
+        self._map_idle_ids()
+        return {"idle_veh": st["out"], "idle_node": blk[1]}
+
+    def _map_idle_ids(self):
+        """Vehicle positions of the heads block -> ``Vehicle.ID`` into the ``idle_veh`` tensor (no-op where they are the same numbers)."""
+        import torch
+        st = getattr(self, "_idle_ids_state", None)
+        if st is None or st.get("table") is None or st.get("out") is None:
+            return
+        pos = st["blk"][0]
+        st["out"].copy_(torch.where(pos >= 0, st["table"][pos.clamp(min=0).long()], pos))
 
     def _outcome_views(self):
         blk = self.env.outcomes_torch()
@@ -637,9 +677,9 @@ class Simulation(object):
         captured (the reason is kept in ``self.BatchedPolicyGraphError``; the caller then runs slot by slot)."""
         import torch
         st = getattr(self, "_bp_state", None)
-        # (dropped by every load of orders - _build_orders_and_env; keyed by the outcome block's address too, which the outcome switch
-        # of the same handle changes)
-        outc = self._outcome_block_ptr()
+        # (dropped by every load of orders - _build_orders_and_env; keyed by the addresses of the outcome block and of the idle-heads
+        # block too, which their switches change on the same handle)
+        outc = (self._outcome_block_ptr(), self.env.idle_heads_device_ptr(self._idle_heads_L) if self._idle_heads_L else None)
         if st is not None and st["env"] is self.env and st.get("outc") == outc:
             return st if st["graph"] is not None else None        # (a capture that failed on this handle is not tried again)
         if st is not None and st["env"] is self.env:
@@ -653,6 +693,7 @@ class Simulation(object):
             acts = None
             with torch.cuda.stream(side):
                 for _ in range(2):
+                    self._map_idle_ids()
                     a = self.BatchedPolicy(obs)
                     if acts is None:
                         acts = torch.empty_like(a)
@@ -663,6 +704,7 @@ class Simulation(object):
                 raise Exception("BatchedPolicy must return an int32 tensor [Replicas, K, 3]")
             g = torch.cuda.CUDAGraph(keep_graph=True)
             with torch.cuda.graph(g):
+                self._map_idle_ids()                              # (BatchedIdleHeads with driver ids: part of the captured slot)
                 acts.copy_(self.BatchedPolicy(obs))
         except Exception as e:
             self.BatchedPolicyGraphError = repr(e)
@@ -793,6 +835,8 @@ class Simulation(object):
                 self.BatchedObs = {k: ob[i] for i, k in enumerate(names)}
                 if self._outcomes_on:
                     self.BatchedOutcomes = self._outcome_views()
+                if self._idle_heads_L:
+                    self.BatchedObs.update(self._idle_head_views())
                 t = dt.datetime.now(); self.RewardFunction(); self.TotallyRewardTime += dt.datetime.now() - t
                 t = dt.datetime.now(); self.GetNextStateFunction(); self.TotallyNextStateTime += dt.datetime.now() - t
                 t = dt.datetime.now(); self.LearningFunction(); self.TotallyLearningTime += dt.datetime.now() - t
@@ -800,7 +844,7 @@ class Simulation(object):
                 t = dt.datetime.now()
                 acts = self.DispatchFunction()
                 if acts is None and self._policy_overridden():        # (the policy form, slot by slot: other hooks overridden, or no capture)
-                    acts = self.BatchedPolicy({k: self.BatchedObs[k] for k in self.BatchedPolicyPlanes})
+                    acts = self.BatchedPolicy({k: self.BatchedObs[k] for k in tuple(self.BatchedPolicyPlanes) + (("idle_veh", "idle_node") if self._idle_heads_L else ())})
                 if acts is not None:
                     self.env.apply_dispatch_torch(acts)
                 self.TotallyDispatchTime += dt.datetime.now() - t
