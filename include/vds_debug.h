@@ -61,6 +61,29 @@ int vds_debug_cluster_forms(vds_handle *h, uint8_t *out, int64_t cap, int32_t *n
  * dense layout, no neighbour search); words past 10 are -1. */
 int vds_debug_layout(vds_handle *h, int32_t *out, int32_t cap);
 
+/* Host tables of a load without a handle or a device (csrc/vds_tables.h; tests/test_order_tables.py): the city of vds_load_static
+ * (nbr_off null: no neighbour search) and n_days order days of vds_load_order_days, built with `threads` workers.  Out: day_out
+ * [n_days][4] {T, now0, Oq, q_base}; sizes [8] {n processed orders, entries of bkt_off, of tick_off, m arrival slots, entries of d_first,
+ * W, hmax, verdict on the static arrival slots (every_order != 0: only if every processed order owns one)}; so_rec [n][4], ord_q,
+ * so_rank, so_slot [n] (cap_rec: orders these four hold), bkt_off, tick_off, d_rec [m][2], d_first with their capacities in elements
+ * (rows for d_rec).  VDS_ECAPACITY when an array is short (sizes is complete, short arrays are left alone); after any other failure err
+ * holds the text vds_last_error would give. */
+int vds_debug_order_tables(const int32_t *cost, int32_t N, const int32_t *node2cluster, int32_t C, int32_t tick_minutes,
+                           const int32_t *nbr_off, const int32_t *nbr_idx, int32_t depth_limit, int32_t ring_ticks,
+                           int32_t n_days, const int64_t *day_off, const int32_t *release_min, const int32_t *pickup,
+                           const int32_t *delivery, int32_t threads, int32_t every_order, int32_t *day_out, int64_t *sizes,
+                           int32_t *so_rec, int32_t *ord_q, int32_t *so_rank, int32_t *so_slot, int64_t cap_rec,
+                           int32_t *bkt_off, int64_t cap_bkt, int32_t *tick_off, int64_t cap_tick, int32_t *d_rec, int64_t cap_drec,
+                           int32_t *d_first, int64_t cap_first, char *err, int32_t err_cap);
+
+/* The storage order of the replicas for a replica -> day map (vds_set_replica_days): gran_small_ok - day groups of 8 / 4 replicas may
+ * be used, regroup_ok - the replicas may be stored regrouped by day, alloc_replicas - stored replicas of state tables at hand (0: none).
+ * head [4] {R, row_gran, chunk_days, regrouped}; int_to_ext, rperm, day_of_internal [R] (cap: entries they hold; -1 / -1 / n_days for a
+ * dummy replica, the identity when not regrouped), ext_to_int [R_ext].  VDS_ECAPACITY when R > cap (head is complete). */
+int vds_debug_replica_plan(const int32_t *replica_day, int32_t R_ext, int32_t n_days, int32_t gran_small_ok, int32_t regroup_ok,
+                           int32_t alloc_replicas, int32_t *head, int32_t *int_to_ext, int32_t *rperm, int32_t *day_of_internal,
+                           int32_t cap, int32_t *ext_to_int);
+
 /* DPP primitives of the kernels on nwaves x 64 int32 values (tests/test_gpu_primitives.py): out_wave [nwaves] wavefront
  * minima; out_rowmin / out_rowsum / out_rowscan [nwaves * 64] per-lane 16-lane-row minimum, row sum and inclusive row scan */
 int vds_selftest_dpp(vds_handle *h, const int32_t *in, int32_t *out_wave, int32_t *out_rowmin, int32_t *out_rowsum,

@@ -4,6 +4,7 @@
 #include "../../include/vds_debug.h"
 #include "vds_device.h"
 #include "vds_launch.h"
+#include "vds_tables.h"
 
 #include <algorithm>
 #include <unordered_map>
@@ -19,6 +20,7 @@
 #include <mutex>
 #include <new>
 #include <numeric>
+#include <optional>
 #include <string>
 #include <vector>
 #include <execinfo.h>
@@ -29,36 +31,7 @@ using namespace vds;
 
 static thread_local std::string g_create_error;
 
-// One loaded order day on the host side (the device side is vds::DayDesc)
-struct DayHost {
-    int O = 0;                           // all orders of the day incl. never-processed ones
-    int T = 0, now0 = 0, q_base = 0, Oq = 0;
-    std::vector<int> so_id;              // q - q_base -> order id
-    std::vector<int> q_value;            // q - q_base -> OrderValue (:341-342)
-    std::vector<int> q_of;               // order id -> q - q_base, -1 never processed (built on first use by the dense read side)
-    std::vector<int> o_tick;             // order id -> tick (or -1 never processed)
-    std::vector<long long> value_upto;   // [T+1] prefix of OrderValue of processed orders by tick
-    long long value_all = 0;
-};
-
-// host tables that are written completely before they are read (the sorted order records of a load: 50 MB at 16 days): resize()
-// default-initialises, so the pages are first touched by the day workers that fill them, not zeroed by the calling thread first
-template <typename T>
-struct NoInitAlloc {
-    using value_type = T;
-    NoInitAlloc() = default;
-    template <class U> NoInitAlloc(const NoInitAlloc<U> &) {}
-    T *allocate(size_t n) { return static_cast<T *>(::operator new(n * sizeof(T))); }
-    void deallocate(T *p, size_t) { ::operator delete(p); }
-    template <class U, class... A> void construct(U *p, A &&...a) {
-        if constexpr (sizeof...(A) == 0) ::new ((void *)p) U; else ::new ((void *)p) U(std::forward<A>(a)...);
-    }
-    bool operator==(const NoInitAlloc &) const { return true; }
-    bool operator!=(const NoInitAlloc &) const { return false; }
-};
-template <typename T> using hvec = std::vector<T, NoInitAlloc<T>>;
-
-// ... and the largest of them in PINNED host memory (the sorted order records, the arrival-slot records and indices: 90 MB at 16 days,
+// the largest host tables of a load in PINNED host memory (the sorted order records, the arrival-slot records and indices: 90 MB at 16 days,
 // uploaded at ~5 GB/s from pageable memory - 18 of a 16-day load's 50 ms - and at the link's rate from pinned).  Page-locking costs
 // milliseconds per block, so blocks are pooled per process and handed out again (a Reload asks for the same sizes); a block that
 // cannot be pinned is ordinary memory.
@@ -124,7 +97,7 @@ struct vds_handle {
     std::string err;
     bool have_static = false, have_orders = false, have_reset = false;
     bool dfs_mode = false;
-    bool dfs2_ok = false;   // k_tick_replica2 preconditions hold (see vds_kernels.hip)
+    bool dfs2_ok = false;   // k_tick_replica2 preconditions hold (load_days_body)
     bool hybrid_ok = false; // hybrid neighbour-search tick (k_tick_rows in stamp mode + k_dfs_walk) preconditions hold
     long long blk_ints = 0; // total size of the per-cluster cost blocks
     // dense layout (k_tick_dense): static preconditions, the layout the state tables were allocated for
@@ -146,6 +119,7 @@ struct vds_handle {
     std::vector<int4> pull_desc;             // per day {d_first base, d_rec base, TA, 0} (static arrival slots of the dense tick)
     int pull_Od_max = 0;
     std::vector<int> cl_cmax;                // [C] largest cost inside the cluster's block
+    std::vector<int4> cdesc_dense_host;      // host copy of Static.cdesc_dense (empty: no dense blocks)
     int dbg_dense_lpr = 0, dbg_dense_tab = 0, dbg_dense_keys = 0, dbg_dense_slow = 0;      // vds_debug_dense (0: defaults)
     int cost_min = 0, cost_max = 0;
     int max_seq = 0;        // longest visit sequence of FindServerVehicleFunction over the clusters
@@ -292,6 +266,14 @@ static void dev_free(void *p) {
     }
     (void)hipFree(p);
 }
+
+// dev_alloc / upload register their tables in `to` until the scope ends, then again where they did before
+struct AllocInto {
+    vds_handle *h; std::vector<void *> *old;
+    AllocInto(vds_handle *h_, std::vector<void *> *to) : h(h_), old(h_->alloc_sink) { h->alloc_sink = to; }
+    AllocInto(const AllocInto &) = delete;
+    ~AllocInto() { h->alloc_sink = old; }
+};
 
 template <typename T>
 static int dev_alloc(vds_handle *h, T **p, size_t n) {
@@ -493,22 +475,11 @@ static int dev_copy_sync(vds_handle *h) {
 
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-// the order days of one vds_load_order_days call are independent until their tables are laid back to back: worker threads take days
-// off a counter (at most 16, VDS_LOAD_THREADS overrides; one day: the calling thread).  fn(d) must not throw.
-template <typename F>
-static void for_each_day(int n_days, F &&fn) {
+// worker threads of the order-day builders (vds_tables.h: for_each_day caps them at 16 and at the number of days); VDS_LOAD_THREADS overrides
+static int load_threads() {
     int nt = (int)std::thread::hardware_concurrency();
     if (const char *v = getenv("VDS_LOAD_THREADS")) { if (*v) nt = atoi(v); }
-    nt = std::max(1, std::min(std::min(nt, 16), n_days));
-    if (nt <= 1) { for (int d = 0; d < n_days; ++d) fn(d); return; }
-    std::atomic<int> next{0};
-    auto work = [&] { for (int d = next.fetch_add(1); d < n_days; d = next.fetch_add(1)) fn(d); };
-    std::vector<std::thread> th;
-    th.reserve((size_t)nt);
-    // (std::system_error from a thread limit: the workers already started keep going, the calling thread takes what is left)
-    try { for (int i = 1; i < nt; ++i) th.emplace_back(work); } catch (...) { }
-    work();
-    for (auto &t : th) t.join();
+    return nt;
 }
 struct LoadTimer {       // VDS_LOAD_TIMING=1: where vds_load_orders* spends its time, to stderr
     bool on; std::chrono::steady_clock::time_point t0;
@@ -675,28 +646,6 @@ int vds_set_stream(vds_handle *h, void *hip_stream) {
     return VDS_OK;
 }
 
-// FindServerVehicleFunction (:978-996): clusters in the order the recursion marks them visited, start cluster
-// first.  Depth-limited and global-visited (quirk Q4: a cluster first reached on a deep branch is not revisited
-// from a shallower one).  Explicit stack: the walk can be C levels deep.
-static void dfs_visit(int start, int limit, const int32_t *off, const int32_t *idx, std::vector<char> &seen, std::vector<int> &seq) {
-    struct Frame { int k, next, deep; };
-    std::vector<Frame> stack;
-    if (limit < 0) return;                         // `deep > NeighborServerDeepLimit` already at deep 0
-    seen[start] = 1;
-    seq.push_back(start);
-    stack.push_back({start, off[start], 0});
-    while (!stack.empty()) {
-        Frame &f = stack.back();
-        if (f.next >= off[f.k + 1]) { stack.pop_back(); continue; }
-        const int j = idx[f.next++];
-        const int deep = f.deep + 1;
-        if (deep > limit || seen[j]) continue;
-        seen[j] = 1;
-        seq.push_back(j);
-        stack.push_back({j, off[j], deep});        // (invalidates f; not used again this iteration)
-    }
-}
-
 static int dfs_sequences_impl(const int32_t *nbr_off, const int32_t *nbr_idx, int32_t C, int32_t depth_limit,
                       int32_t *seq_off, int32_t *seq, int64_t cap) {
     if (!nbr_off || !seq_off || C < 1 || (cap > 0 && !seq)) return VDS_EINVAL;
@@ -741,202 +690,53 @@ static int load_static_impl(vds_handle *h, const int32_t *cost, int32_t N, const
         }
     }
     S.reject_threshold = h->cfg.pickup_reject_threshold;
-    h->node2cluster.assign(node2cluster, node2cluster + N);
-    h->cl_off.assign(C + 1, 0);
-    for (int n = 0; n < N; ++n) {
-        int c = node2cluster[n];
-        if (c >= C) return fail(h, VDS_EINVAL, "vds_load_static: node2cluster[%d]=%d >= C", n, c);
-        if (c >= 0) h->cl_off[c + 1]++;
-    }
-    int max_nc = 0;
-    for (int c = 0; c < C; ++c) { max_nc = std::max(max_nc, h->cl_off[c + 1]); h->cl_off[c + 1] += h->cl_off[c]; }
-    if (max_nc > 32767) return fail(h, VDS_EINVAL, "vds_load_static: cluster of %d nodes > 32767 unsupported", max_nc);
+    CityTables T;
+    std::string msg;
+    int rc = build_city_tables(cost, N, node2cluster, C, h->cfg.neighbor_can_server ? nbr_off : nullptr, nbr_idx, depth_limit, T, msg);
+    if (rc) return fail(h, rc, "%s", msg.c_str());
+    const int max_nc = T.max_nc;
     S.max_nc = max_nc;
-    h->cl_nodes.assign(h->cl_off[C], 0);
-    h->node_local.assign(N, -1);
-    {
-        std::vector<int> fill(h->cl_off.begin(), h->cl_off.end() - 1);
-        for (int n = 0; n < N; ++n) {
-            int c = node2cluster[n];
-            if (c < 0) continue;
-            h->node_local[n] = fill[c] - h->cl_off[c];
-            h->cl_nodes[fill[c]++] = n;
-        }
-    }
-    // per-cluster cost blocks: blk[c][p][l] = RoadCost(node_l, node_p) = cost[node_p*N + node_l] (:929)
-    std::vector<long long> blk_off(C + 1, 0);
-    for (int c = 0; c < C; ++c) {
-        long long nc = h->cl_off[c + 1] - h->cl_off[c];
-        blk_off[c + 1] = blk_off[c] + (nc * nc + 3) / 4 * 4;   // 16-byte aligned blocks
-    }
-    if (blk_off[C] >= (1ll << 31)) return fail(h, VDS_EINVAL, "vds_load_static: cluster cost blocks exceed 2^31 entries");
-    h->blk_ints = blk_off[C];
-    std::vector<int4> cdesc(C);
-    for (int c = 0; c < C; ++c) cdesc[c] = make_int4(h->cl_off[c + 1] - h->cl_off[c], (int)blk_off[c], 0, 0);
-    std::vector<int> blk((size_t)blk_off[C]);
-    for (int c = 0; c < C; ++c) {
-        int nc = h->cl_off[c + 1] - h->cl_off[c];
-        const int *nodes = h->cl_nodes.data() + h->cl_off[c];
-        int *dst = blk.data() + blk_off[c];
-        for (int p = 0; p < nc; ++p)
-            for (int l = 0; l < nc; ++l) dst[(size_t)p * nc + l] = cost[(size_t)nodes[p] * N + nodes[l]];
-    }
-    // neighbour-search visit sequences (quirks Q4, Q5)
+    h->blk_ints = T.blk_off[C];
     h->depth_limit = depth_limit;
-    std::vector<int> dfs_off(C + 1, 0), dfs_seq;
-    bool any_seq = false;
-    if (h->cfg.neighbor_can_server) {
-        if (!nbr_idx && nbr_off[C] > 0) return fail(h, VDS_EINVAL, "vds_load_static: nbr_idx is null");
-        for (int k = 0; k < nbr_off[C]; ++k)
-            if (nbr_idx[k] < 0 || nbr_idx[k] >= C) return fail(h, VDS_EINVAL, "vds_load_static: neighbour index out of range");
-        std::vector<char> seen(C);
-        std::vector<int> seq;
-        for (int c = 0; c < C; ++c) {
-            seq.clear();
-            if (nbr_off[c + 1] > nbr_off[c]) {          // `elif self.NeighborCanServer and len(NowCluster.Neighbor)` :936
-                std::fill(seen.begin(), seen.end(), 0);
-                dfs_visit(c, depth_limit, nbr_off, nbr_idx, seen, seq);
-            }
-            for (size_t i = 1; i < seq.size(); ++i) dfs_seq.push_back(seq[i]);   // position 0 is c itself
-            dfs_off[c + 1] = (int)dfs_seq.size();
-            if (seq.size() > 1) any_seq = true;
-        }
-    }
-    h->dfs_mode = any_seq;
+    h->dfs_mode = T.any_seq;
+    S.u8_ok = T.u8_ok ? 1 : 0;
+    h->max_seq = T.max_seq; S.seq_pad = T.seq_pad;
     // upload
-    int rc;
-    h->cost_host.assign(cost, cost + (size_t)N * N);
     int *d;
     long long *dl;
-    std::vector<int> costp_host;
-    {
-        // device copy with CLUSTER-CONTIGUOUS columns: column cl_off[c] + l holds node cl_nodes[cl_off[c] + l], so a
-        // vehicle's cost-row index is (cluster offset + loc_local) with no node-table lookup on the device
-        std::vector<int> &costp = costp_host;
-        costp.assign((size_t)N * N, 0);
-        const int ncol = h->cl_off[C];
-        for (int i = 0; i < N; ++i) {
-            const int *src = cost + (size_t)i * N;
-            int *dst = costp.data() + (size_t)i * N;
-            for (int j = 0; j < ncol; ++j) dst[j] = src[h->cl_nodes[j]];
-        }
-        if ((rc = upload(h, &d, costp))) return rc; S.cost = d;
+    unsigned char *d8;
+    int4 *d4;
+    if ((rc = upload(h, &d, T.costp))) return rc; S.cost = d;
+    if ((rc = upload(h, &d, T.node2cluster))) return rc; S.node2cluster = d;
+    if ((rc = upload(h, &d, T.node_local))) return rc; S.node_local = d;
+    if ((rc = upload(h, &d, T.cl_off))) return rc; S.cl_off = d;
+    if ((rc = upload(h, &d, T.cl_nodes))) return rc; S.cl_nodes = d;
+    if ((rc = upload(h, &dl, T.blk_off))) return rc; S.blk_off = dl;
+    if ((rc = upload(h, &d, T.blk))) return rc; S.blk = d;
+    if ((rc = upload(h, &d, T.corder))) return rc; S.corder = d;
+    if ((rc = upload(h, &d8, T.blk8))) return rc; S.blk8 = d8;
+    if ((rc = upload(h, &d4, T.cdesc))) return rc; S.cdesc = d4;
+    S.cost8 = nullptr; S.lbc = nullptr;
+    if (T.u8_ok) { if ((rc = upload(h, &d8, T.cost8))) return rc; S.cost8 = d8; }
+    if (!T.lbc.empty()) { if ((rc = upload(h, &d8, T.lbc))) return rc; S.lbc = d8; }
+    if ((rc = upload(h, &d4, T.cdesc_ord))) return rc; S.cdesc_ord = d4;
+    S.blk8s = nullptr; S.blk32s = nullptr; S.cdesc_dense = nullptr;
+    if (T.dense_ok) {
+        if ((rc = upload(h, &d8, T.blk_dense))) return rc;
+        if (T.dense_bytes) S.blk8s = d8; else S.blk32s = reinterpret_cast<const int *>(d8);
+        if ((rc = upload(h, &d4, T.cdesc_dense))) return rc; S.cdesc_dense = d4;
     }
-    if ((rc = upload(h, &d, h->node2cluster))) return rc; S.node2cluster = d;
-    if ((rc = upload(h, &d, h->node_local))) return rc; S.node_local = d;
-    if ((rc = upload(h, &d, h->cl_off))) return rc; S.cl_off = d;
-    if ((rc = upload(h, &d, h->cl_nodes))) return rc; S.cl_nodes = d;
-    if ((rc = upload(h, &dl, blk_off))) return rc; S.blk_off = dl;
-    if ((rc = upload(h, &d, blk))) return rc; S.blk = d;
-    {
-        std::vector<int> corder(C);
-        for (int c = 0; c < C; ++c) corder[c] = c;
-        std::stable_sort(corder.begin(), corder.end(), [&](int a, int b) { return cdesc[a].x > cdesc[b].x; });
-        if ((rc = upload(h, &d, corder))) return rc; S.corder = d;
-        h->corder_host = corder;
-        std::vector<int4> cdo(C);
-        // byte copy of the blocks for the fast kernel (filled below once the cost range is known)
-        std::vector<long long> b8off(C + 1, 0);
-        for (int c = 0; c < C; ++c) { long long nc = cdesc[c].x; b8off[c + 1] = b8off[c] + (nc * nc + 15) / 16 * 16; }
-        bool u8 = b8off[C] < (1ll << 31);
-        for (size_t i = 0; i < blk.size() && u8; ++i) u8 = blk[i] >= 0 && blk[i] <= 255;
-        S.u8_ok = u8 ? 1 : 0;
-        std::vector<unsigned char> blk8(u8 ? (size_t)b8off[C] : 1, 0);
-        if (u8)
-            for (int c = 0; c < C; ++c) {
-                const long long nc = cdesc[c].x;
-                for (long long e = 0; e < nc * nc; ++e) blk8[(size_t)b8off[c] + e] = (unsigned char)blk[(size_t)cdesc[c].y + e];
-            }
-        { unsigned char *d8; if ((rc = upload(h, &d8, blk8))) return rc; S.blk8 = d8; }
-        for (int i = 0; i < C; ++i) cdo[i] = make_int4(cdesc[corder[i]].x, cdesc[corder[i]].y, corder[i], u8 ? (int)b8off[corder[i]] : 0);
-        for (int c = 0; c < C; ++c) cdesc[c].z = u8 ? (int)b8off[c] : 0;
-        { int4 *d4c; if ((rc = upload(h, &d4c, cdesc))) return rc; S.cdesc = d4c; }
-        // byte copy of the whole (column-permuted) matrix for the neighbour search
-        S.cost8 = nullptr;
-        if (u8) {
-            std::vector<unsigned char> c8((size_t)N * N + 16, 0);
-            bool fits = true;
-            for (size_t i = 0; i < (size_t)N * N && fits; ++i) { fits = costp_host[i] >= 0 && costp_host[i] <= 255; c8[i] = (unsigned char)costp_host[i]; }
-            if (fits) { unsigned char *d8; if ((rc = upload(h, &d8, c8))) return rc; S.cost8 = d8; }
-            else S.u8_ok = 0;
-            S.lbc = nullptr;
-            h->lbc_host.clear();
-            if (fits && any_seq && (long long)N * C <= (256ll << 20)) {
-                // per (pickup node, cluster): the cheapest way from any node of the cluster - prunes the neighbour search
-                std::vector<unsigned char> lb((size_t)N * C, 255);
-                for (int pn = 0; pn < N; ++pn) {
-                    const unsigned char *row = c8.data() + (size_t)pn * N;
-                    for (int c = 0; c < C; ++c) {
-                        unsigned char m = 255;
-                        for (int col = h->cl_off[c]; col < h->cl_off[c + 1]; ++col) m = std::min(m, row[col]);
-                        lb[(size_t)pn * C + c] = m;
-                    }
-                }
-                unsigned char *dlb; if ((rc = upload(h, &dlb, lb))) return rc; S.lbc = dlb;
-                h->lbc_host.swap(lb);
-            }
-        }
-        { int4 *d4o; if ((rc = upload(h, &d4o, cdo))) return rc; S.cdesc_ord = d4o; }
-        // dense layout (k_tick_dense): cost blocks with row stride n_c + 1 whose extra column holds the dead cost - the loc byte of a
-        // taken / absent idle entry names that column, so such an entry loses every comparison without a test in the match loop.
-        // Bytes (column value 0xFF) when every cost is <= 254, ints (DENSE_DEAD_COST) otherwise.
-        S.blk8s = nullptr; S.blk32s = nullptr; S.cdesc_dense = nullptr;
-        bool d_ok = max_nc <= 255;
-        bool d8 = d_ok && S.u8_ok;
-        for (size_t i = 0; i < blk.size() && d8; ++i) d8 = blk[i] <= 254;
-        if (d_ok) {
-            std::vector<long long> doff(C, 0);
-            long long tot = 0;
-            const long long esz = d8 ? 1 : 4;
-            for (int c = 0; c < C; ++c) { const long long nc = cdesc[c].x; doff[c] = tot; tot += (nc * (nc + 1) * esz + 15) / 16 * 16; }      // byte offsets, 16-byte aligned
-            d_ok = tot < (1ll << 31);
-            if (d_ok) {
-                std::vector<unsigned char> bs((size_t)std::max<long long>(tot, 16), 0);
-                for (int c = 0; c < C; ++c) {
-                    const long long nc = cdesc[c].x;
-                    for (long long pp = 0; pp < nc; ++pp) {
-                        for (long long l = 0; l <= nc; ++l) {
-                            const int v = l < nc ? blk[(size_t)cdesc[c].y + pp * nc + l] : (d8 ? 0xFF : DENSE_DEAD_COST);
-                            if (d8) bs[(size_t)(doff[c] + pp * (nc + 1) + l)] = (unsigned char)v;
-                            else memcpy(bs.data() + (size_t)(doff[c] + (pp * (nc + 1) + l) * 4), &v, 4);
-                        }
-                    }
-                }
-                unsigned char *db; if ((rc = upload(h, &db, bs))) return rc;
-                if (d8) S.blk8s = db; else S.blk32s = reinterpret_cast<const int *>(db);
-                std::vector<int4> cdd(C);
-                // (.w: the cluster has a visit sequence - its unserved orders search the neighbours, :936 - read by the stamp form)
-                for (int i = 0; i < C; ++i) cdd[i] = make_int4(cdesc[corder[i]].x, (int)doff[corder[i]], corder[i], dfs_off[corder[i] + 1] > dfs_off[corder[i]] ? 1 : 0);
-                int4 *d4d; if ((rc = upload(h, &d4d, cdd))) return rc; S.cdesc_dense = d4d;
-            }
-        }
-        h->dense_static_ok = d_ok;
-        // largest RoadCost inside each cluster = the longest PickupWaitTime an order of that cluster can get (:929-933)
-        h->cl_cmax.assign(C, 0);
-        for (int c = 0; c < C; ++c) {
-            const long long nc = cdesc[c].x;
-            int mx = 0;
-            for (long long e = 0; e < nc * nc; ++e) mx = std::max(mx, blk[(size_t)cdesc[c].y + e]);
-            h->cl_cmax[c] = mx;
-        }
-    }
-    h->max_seq = 0;
-    for (int c = 0; c < C; ++c) h->max_seq = std::max(h->max_seq, dfs_off[c + 1] - dfs_off[c]);
-    S.seq_pad = h->max_seq <= 64 ? 64 : h->max_seq <= 128 ? 128 : 256;
-    h->dfs_off_host = dfs_off; h->dfs_seq_host = dfs_seq;
-    if ((rc = upload(h, &d, dfs_off))) return rc; S.dfs_off = d;
-    if ((rc = upload(h, &d, dfs_seq))) return rc; S.dfs_seq = d;
-    {   // the visit sets as a bit matrix (k_dfs_walk: which dry orders see a steal from cluster c')
-        const int bmw = (C + 31) / 32;
-        std::vector<unsigned> vb((size_t)C * bmw, 0u);
-        for (int c = 0; c < C; ++c)
-            for (int j = dfs_off[c]; j < dfs_off[c + 1]; ++j) vb[(size_t)c * bmw + (dfs_seq[j] >> 5)] |= 1u << (dfs_seq[j] & 31);
-        unsigned *dv; if ((rc = upload(h, &dv, vb))) return rc; S.vis_bits = dv;
-    }
+    h->dense_static_ok = T.dense_ok;
+    if ((rc = upload(h, &d, T.dfs_off))) return rc; S.dfs_off = d;
+    if ((rc = upload(h, &d, T.dfs_seq))) return rc; S.dfs_seq = d;
+    { unsigned *dv; if ((rc = upload(h, &dv, T.vis_bits))) return rc; S.vis_bits = dv; }
+    // host mirrors (the blocks and byte copies are not kept)
+    h->node2cluster.swap(T.node2cluster); h->node_local.swap(T.node_local); h->cl_off.swap(T.cl_off); h->cl_nodes.swap(T.cl_nodes);
+    h->cost_host.swap(T.cost); h->corder_host.swap(T.corder); h->cdesc_dense_host.swap(T.cdesc_dense); h->cl_cmax.swap(T.cl_cmax);
+    h->lbc_host.swap(T.lbc); h->dfs_off_host.swap(T.dfs_off); h->dfs_seq_host.swap(T.dfs_seq);
     // fast-kernel preconditions: packed (cost << 7 | position) keys, no window rejects
     {
-        int cmin = 0x7FFFFFFF, cmax = -0x7FFFFFFF - 1;
-        for (size_t i = 0; i < (size_t)N * N; ++i) { cmin = std::min(cmin, cost[i]); cmax = std::max(cmax, cost[i]); }
+        const int cmin = T.cmin, cmax = T.cmax;
         S.fast_ok = (cmin >= 0 && cmax < (1 << 23) && (long long)cmax <= S.reject_threshold) ? 1 : 0;
         S.window_live = ((long long)cmax > S.reject_threshold) ? 1 : 0;
         if (h->cfg.force_generic == 1) S.fast_ok = 0;
@@ -997,8 +797,7 @@ static int alloc_state(vds_handle *h, int O) {
     h->alloc_R = R;
     h->nodes_valid = false;                              // (d_veh_node is re-allocated below)
     int rc;
-    struct Sink { vds_handle *h; std::vector<void *> *old; ~Sink() { h->alloc_sink = old; } } sink{h, h->alloc_sink};
-    h->alloc_sink = &h->state_allocs;
+    AllocInto into(h, &h->state_allocs);
     if ((rc = dev_alloc(h, &D.hdr, B * HDR_WORDS))) return rc;
     if ((rc = dev_alloc(h, &D.cnt, B * CNT_WORDS))) return rc;
     {   // the idle table lives in its own allocation list: vds_reset / vds_set_idle_cap may replace it alone
@@ -1042,9 +841,6 @@ static int alloc_state(vds_handle *h, int O) {
     return VDS_OK;
 }
 
-// self.Orders after CreateAllInstantiate (:325-342) for n_days independent days; replica r replays day replica_day[r].
-static int alloc_state(vds_handle *h, int O);
-
 // The replica -> day map h->replica_day over the resident order days, turned into what the kernels read: the storage order of the
 // replicas (regrouped by day when the map mixes days inside aligned groups of 16 and the padding stays under a quarter - see
 // vds_handle), Static.chunk_days / rperm / replica_day / int2ext / replica_desc / replica_desc2, the length of the batch's day.  Called
@@ -1056,60 +852,16 @@ static int apply_replica_map(vds_handle *h) {
     int Tmax = 0;                                   // the batch steps as long as its longest day that some replica replays
     for (int r = 0; r < RX; ++r) Tmax = std::max(Tmax, h->days[h->replica_day[r]].T);
     S.T = Tmax;
-    S.R = RX; h->int2ext.clear(); h->ext2int.clear();
     // the day groups' granule: aligned groups of 16 replicas on one day - or, on the dense layout at 16 lanes per replica (what order
     // days per replica run with), of 8: k_tick_dense then runs 8-row workgroups
     const bool gran8_ok = S.dense && S.dense_lpr == 16 && h->cfg.force_generic == 0 && !(getenv("VDS_ROW_GRAN8") && getenv("VDS_ROW_GRAN8")[0] == '0');
-    S.row_gran = 16;
-    S.chunk_days = n_days > 1 ? 1 : 0;
-    for (int r = 0; r < RX && S.chunk_days; ++r)
-        if (h->replica_day[r] != h->replica_day[r & ~15]) S.chunk_days = 0;
-    for (int gr = 8; gr >= 4 && n_days > 1 && !S.chunk_days && gran8_ok; gr >>= 1) {
-        bool okg = true;
-        for (int r = 0; r < RX && okg; ++r) okg = h->replica_day[r] == h->replica_day[r & ~(gr - 1)];
-        if (okg) { S.chunk_days = 1; S.row_gran = gr; }
-    }
-    // a map that mixes days inside aligned groups of 16 replicas: the replicas are STORED regrouped by day (see vds_handle),
-    // every day's last group padded with dummy replicas, when the padding stays under a quarter; otherwise every 16-lane row
-    // of the fast kernel gets its own order stream (day mode 2)
-    std::vector<int> rperm;          // row slot -> internal replica, -1 for a dummy (k_tick_rows skips those rows)
-    std::vector<int> day_of_internal;
-    if (n_days > 1 && !S.chunk_days && h->cfg.force_generic == 0) {
-        std::vector<std::vector<int>> by_day(n_days);
-        for (int r = 0; r < RX; ++r) by_day[h->replica_day[r]].push_back(r);
-        std::vector<int> i2e;
-        int gran = 16;
-        for (int pass = 0; pass < 3; ++pass, gran >>= 1) {
-            i2e.clear(); day_of_internal.clear();
-            for (int dd = 0; dd < n_days; ++dd) {
-                for (int r : by_day[dd]) { i2e.push_back(r); day_of_internal.push_back(dd); }
-                while (i2e.size() % gran) { i2e.push_back(-1); day_of_internal.push_back(n_days); }      // dummy: replays the empty day
-            }
-            if (i2e.size() * 4 <= (size_t)RX * 5 || !gran8_ok) break;      // (too much padding with groups of 16: groups of 8, then of 4)
-        }
-        while (i2e.size() % 16) { i2e.push_back(-1); day_of_internal.push_back(n_days); }      // (the replica count stays a multiple of 16)
-        if (i2e.size() * 4 <= (size_t)RX * 5) {
-            S.row_gran = gran >= 16 ? 16 : (gran >= 8 ? 8 : 4);
-            // (a handle that already stores more padded replicas keeps that many: the state tables are strided by S.R, and a map
-            // whose padding differs by a group must not re-allocate them - vds_set_replica_days every episode)
-            if (h->alloc_R > (int)i2e.size() && (size_t)h->alloc_R * 4 <= (size_t)RX * 5 && !h->state_allocs.empty())
-                while ((int)i2e.size() < h->alloc_R) { i2e.push_back(-1); day_of_internal.push_back(n_days); }
-            S.chunk_days = 1;
-            S.R = (int)i2e.size();
-            h->int2ext = i2e;
-            h->ext2int.assign(RX, -1);
-            for (int i = 0; i < S.R; ++i) if (i2e[i] >= 0) h->ext2int[i2e[i]] = i;
-            rperm.resize(S.R);
-            for (int i = 0; i < S.R; ++i) rperm[i] = i2e[i] >= 0 ? i : -1;
-        } else {
-            day_of_internal.clear();
-        }
-    }
-    if (day_of_internal.empty()) day_of_internal = h->replica_day;
+    ReplicaPlan P = plan_replicas(h->replica_day.data(), RX, n_days, gran8_ok, h->cfg.force_generic == 0, h->state_allocs.empty() ? 0 : h->alloc_R);
+    S.R = P.R; S.row_gran = P.row_gran; S.chunk_days = P.chunk_days;
+    h->int2ext.swap(P.int2ext); h->ext2int.swap(P.ext2int);
+    const std::vector<int> &rperm = P.rperm, &day_of_internal = P.day_of_internal;
     for (void *p : h->map_allocs) dev_free(p);
     h->map_allocs.clear();
-    struct Sink { vds_handle *h; std::vector<void *> *old; ~Sink() { h->alloc_sink = old; } } sink{h, h->alloc_sink};
-    h->alloc_sink = &h->map_allocs;
+    AllocInto into(h, &h->map_allocs);
     int rc;
     int *d;
     S.rperm = nullptr; S.rslots = 0; S.int2ext = nullptr;
@@ -1148,8 +900,7 @@ static int alloc_results(vds_handle *h) {
     h->result_allocs.clear();
     h->D.out = nullptr; h->D.arr = nullptr; h->D.slog = nullptr;
     h->res_cap_out = h->res_cap_arr = h->res_cap_slog = 0;
-    struct Sink { vds_handle *h; std::vector<void *> *old; ~Sink() { h->alloc_sink = old; } } sink{h, h->alloc_sink};
-    h->alloc_sink = &h->result_allocs;
+    AllocInto into(h, &h->result_allocs);
     int rc = dev_alloc(h, &h->D.out, need_out);
     if (!rc && need_arr) rc = dev_alloc(h, &h->D.arr, need_arr);
     if (!rc && need_slog) rc = dev_alloc(h, &h->D.slog, need_slog);
@@ -1175,7 +926,6 @@ static int set_replica_days_impl(vds_handle *h, const int32_t *replica_day) {
         // tables are strided by S.R - the slow path, allocations
         if ((rc = alloc_state(h, h->alloc_O))) return rc;
         if ((rc = alloc_results(h))) return rc;
-        if (h->d_veh_stage) { /* sized by R_ext: unchanged */ }
     }
     { h->run_stale = true; h->tables_gen++; }
     h->have_reset = false;                              // the episode state belongs to the previous map: vds_reset* must follow
@@ -1208,7 +958,7 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
     }
     lt.lap("sync + free the previous day");
     Static &S = h->S;
-    const int N = S.N, C = S.C, tick = S.tick_minutes;
+    const int N = S.N, C = S.C;
     const int RX = h->R_ext;
     S.R = RX; S.int2ext = nullptr; h->int2ext.clear(); h->ext2int.clear();
     h->replica_day.assign(RX, 0);
@@ -1219,165 +969,38 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
         if (d < 0 || d >= n_days) return fail(h, VDS_EINVAL, "vds_load_order_days: replica %d is mapped to day %d of %d", r, d, n_days);
         h->replica_day[r] = d;
     }
-    h->days.assign(n_days, DayHost());
-    pvec<int4> so_rec;                    // (every position is written by its day's worker: bucket fill / cursor order; pinned: uploaded whole)
-    hvec<int> bkt_off, tick_off, ord_q, so_pnode;
-    std::vector<DayDesc> ddesc(n_days);
-    int Tmax = 0, Oqmax = 0, Omax = 0, mto = 0;
-    long long Ototal = 0;
-    {
-        // (a) per day, in parallel: SimCity's prologue, OrderValue, the cursor of MatchFunction, bucket counts
-        struct DayLocal { int O = 0, T = 0, n_proc = 0, day_mto = 0, code = 0; long long now0 = 0; std::vector<int> value, cnt, toff; std::string msg; };
-        std::vector<DayLocal> L(n_days);
-        auto day_fail = [](DayLocal &l, int code, const char *fmt, long long a, long long b) { char buf[256]; snprintf(buf, sizeof(buf), fmt, a, b); l.code = code; l.msg = buf; };
-        for_each_day(n_days, [&](int d) {
-            DayLocal &l = L[d];
-            try {
-                DayHost &H = h->days[d];
-                const int32_t *rel = release_min + day_off[d], *pk = pickup + day_off[d], *dl = delivery + day_off[d];
-                const int O = (int)(day_off[d + 1] - day_off[d]);
-                // SimCity prologue :1037-1040
-                const long long now0 = (long long)rel[0] - tick;
-                const long long end = (long long)rel[O - 1] + 3LL * tick;
-                const int T = end >= now0 ? (int)((end - now0) / tick) + 1 : 0;
-                if (T > 65535) { day_fail(l, VDS_EINVAL, "vds_load_orders: %lld ticks > 65535 unsupported", T, 0); return; }
-                l.O = O; l.T = T; l.now0 = now0;
-                H.O = O; H.T = T; H.now0 = (int)now0;
-                l.value.resize(O);
-                const std::vector<int> &costh = h->cost_host;
-                for (int i = 0; i < O; ++i) {
-                    if (pk[i] < 0 || pk[i] >= N || dl[i] < 0 || dl[i] >= N) { day_fail(l, VDS_EINVAL, "vds_load_orders: order %lld has a node outside [0,%lld)", i, N); return; }
-                    l.value[i] = costh[(size_t)dl[i] * N + pk[i]];           // :341-342
-                }
-                // the cursor of MatchFunction (:912-973): order i is processed at the first tick whose window
-                // covers every order up to i; the last order is never processed (quirk Q1, :914-915)
-                H.o_tick.assign(O, -1);
-                l.cnt.assign((size_t)T * C + 1, 0);
-                long long run = 0;
-                int n_proc = 0;
-                H.value_all = 0;
-                for (int i = 0; i < O; ++i) {
-                    H.value_all += l.value[i];
-                    long long x = (long long)rel[i] - now0;
-                    long long ti = x < 0 ? 0 : x / tick;
-                    run = std::max(run, ti);
-                    if (i == O - 1 || run >= T) continue;
-                    int pc = h->node2cluster[pk[i]], dc = h->node2cluster[dl[i]];
-                    if (pc < 0 || dc < 0) { day_fail(l, VDS_ESTATE, "vds_load_orders: order %lld touches a node outside every cluster (KeyError in the reference, :918/:960)", i, 0); return; }
-                    H.o_tick[i] = (int)run;
-                    l.cnt[(size_t)run * C + pc + 1]++;
-                    n_proc++;
-                }
-                for (size_t i = 1; i < l.cnt.size(); ++i) l.cnt[i] += l.cnt[i - 1];
-                l.n_proc = n_proc;
-            } catch (...) { l.code = VDS_ENOMEM; l.msg = "vds_load_orders: out of host memory"; }
-        });
-        // (b) the days laid back to back
-        std::vector<size_t> rec0(n_days + 1, 0), bk0(n_days + 1, 0), tk0(n_days + 1, 0);
-        for (int d = 0; d < n_days; ++d) {
-            if (L[d].code) return fail(h, L[d].code, "%s", L[d].msg.c_str());
-            rec0[d + 1] = rec0[d] + (size_t)L[d].n_proc;
-            bk0[d + 1] = bk0[d] + L[d].cnt.size();
-            tk0[d + 1] = tk0[d] + (size_t)L[d].T + 1;
-            if (rec0[d + 1] >= (1ull << 31)) return fail(h, VDS_EINVAL, "vds_load_orders: more than 2^31 processed orders on one handle");
-            if (bk0[d + 1] >= (1ull << 31)) return fail(h, VDS_EINVAL, "vds_load_orders: bucket table exceeds 2^31 entries");
-        }
-        so_rec.resize(rec0[n_days]); so_pnode.resize(rec0[n_days]); ord_q.resize(rec0[n_days]);
-        bkt_off.resize(bk0[n_days]); tick_off.resize(tk0[n_days]);
-        // (c) per day, in parallel: the sorted order records (tick, pickup cluster, id), results' bookkeeping
-        for_each_day(n_days, [&](int d) {
-            DayLocal &l = L[d];
-            try {
-                DayHost &H = h->days[d];
-                const int32_t *pk = pickup + day_off[d], *dl = delivery + day_off[d];
-                const int O = l.O, T = l.T, n_proc = l.n_proc;
-                const size_t r0 = rec0[d];
-                H.q_base = (int)r0; H.Oq = n_proc;
-                H.so_id.assign(n_proc, 0);
-                H.q_value.assign(n_proc, 0);
-                H.value_upto.assign(T + 1, 0);
-                l.toff.assign(T + 1, 0);
-                std::vector<int> fill(l.cnt.begin(), l.cnt.end() - 1);
-                int k = 0;
-                for (int i = 0; i < O; ++i) {
-                    int ti = H.o_tick[i];
-                    if (ti < 0) continue;
-                    int pc = h->node2cluster[pk[i]], dc = h->node2cluster[dl[i]];
-                    int q = fill[(size_t)ti * C + pc]++;
-                    so_rec[r0 + q] = make_int4(i, h->node_local[pk[i]] | (h->node_local[dl[i]] << 16), dc | (pc << 16), l.value[i]);
-                    H.so_id[q] = i;
-                    H.q_value[q] = l.value[i];
-                    so_pnode[r0 + q] = pk[i];
-                    ord_q[r0 + k++] = (int)r0 + q;                       // absolute positions
-                    l.toff[ti + 1]++;
-                    H.value_upto[ti + 1] += l.value[i];
-                }
-                for (int t = 0; t < T; ++t) { l.toff[t + 1] += l.toff[t]; H.value_upto[t + 1] += H.value_upto[t]; }
-                int day_mto = 0;
-                for (int t = 0; t < T; ++t) day_mto = std::max(day_mto, l.toff[t + 1] - l.toff[t]);
-                l.day_mto = day_mto;
-                ddesc[d].bkt_base = (int)bk0[d];
-                ddesc[d].tick_base = (int)tk0[d];
-                ddesc[d].now0 = H.now0; ddesc[d].T = T; ddesc[d].q_base = H.q_base; ddesc[d].Oq = n_proc;
-                ddesc[d].max_tick_orders = day_mto; ddesc[d].pad = 0;
-                for (size_t i = 0; i < l.cnt.size(); ++i) bkt_off[bk0[d] + i] = l.cnt[i] + (int)r0;            // absolute positions
-                for (int t = 0; t <= T; ++t) tick_off[tk0[d] + t] = l.toff[t] + (int)r0;
-                std::vector<int>().swap(l.value); std::vector<int>().swap(l.cnt);
-            } catch (...) { l.code = VDS_ENOMEM; l.msg = "vds_load_orders: out of host memory"; }
-        });
-        for (int d = 0; d < n_days; ++d) {
-            if (L[d].code) return fail(h, L[d].code, "%s", L[d].msg.c_str());
-            Tmax = std::max(Tmax, L[d].T); Oqmax = std::max(Oqmax, L[d].n_proc); Omax = std::max(Omax, L[d].O); mto = std::max(mto, L[d].day_mto);
-            Ototal += L[d].O;
-        }
-    }
+    const int nt = load_threads();
+    const CityView city{N, C, S.tick_minutes, h->cost_host.data(), h->node2cluster.data(), h->node_local.data(), h->cl_cmax.data()};
+    std::string msg;
+    int rc;
+    pvec<int4> so_rec;                    // (pinned: uploaded whole)
+    OrderTables ot;
+    if ((rc = build_order_tables(city, n_days, day_off, release_min, pickup, delivery, nt, [&](size_t n) { so_rec.resize(n); return so_rec.data(); }, ot, h->days, msg)))
+        return fail(h, rc, "%s", msg.c_str());
     lt.lap("cursor, buckets, sorted records");
-    S.now0 = h->days[0].now0; S.Oq = Oqmax; h->O = Omax; h->Oqmax = Oqmax;
+    const std::vector<DayDesc> &ddesc = ot.ddesc;
+    const int Omax = ot.Omax, mto = ot.mto;
+    S.now0 = h->days[0].now0; S.Oq = ot.Oqmax; h->O = Omax; h->Oqmax = ot.Oqmax;
     S.n_days = n_days;
-    (void)Tmax;
-    {   // the empty day of padding replicas (storage regrouped by day): over before its first slot.  Always there, last.
-        DayDesc e{}; e.bkt_base = 0; e.tick_base = 0; e.now0 = h->days[0].now0; e.T = 0; e.q_base = 0; e.Oq = 0; e.max_tick_orders = 0; e.pad = 0;
-        ddesc.push_back(e);
-    }
     h->ddesc_host = ddesc;
     S.max_tick_orders = mto;
-    int rc;
     int *d;
     int4 *d4;
-    struct Sink { vds_handle *h; ~Sink() { h->alloc_sink = nullptr; } } sink{h};
-    h->alloc_sink = &h->order_allocs;
+    std::optional<AllocInto> into(std::in_place, h, &h->order_allocs);
     if ((rc = upload(h, &d4, so_rec))) return rc; S.so_rec = d4;
-    if ((rc = upload(h, &d, bkt_off))) return rc; S.bkt_off = d;
-    if ((rc = upload(h, &d, tick_off))) return rc; S.tick_off = d;
-    if ((rc = upload(h, &d, so_pnode))) return rc; S.so_pnode = d;
-    if ((rc = upload(h, &d, ord_q))) return rc; S.ord_q = d;
-    {   // rank of every sorted position inside its slot (tick_off / ord_q hold absolute positions)
-        std::vector<int> so_rank(so_rec.size(), 0);
-        for_each_day(n_days, [&](int dd) {
-            const DayDesc &de = ddesc[dd];
-            for (int t = 0; t < de.T; ++t) {
-                const int a = tick_off[de.tick_base + t], b = tick_off[de.tick_base + t + 1];
-                for (int i = a; i < b; ++i) so_rank[ord_q[i]] = i - a;
-            }
-        });
-        if ((rc = upload(h, &d, so_rank))) return rc; S.so_rank = d;
-    }
+    if ((rc = upload(h, &d, ot.bkt_off))) return rc; S.bkt_off = d;
+    if ((rc = upload(h, &d, ot.tick_off))) return rc; S.tick_off = d;
+    if ((rc = upload(h, &d, ot.so_pnode))) return rc; S.so_pnode = d;
+    if ((rc = upload(h, &d, ot.ord_q))) return rc; S.ord_q = d;
+    if ((rc = upload(h, &d, build_order_ranks(ot, nt)))) return rc; S.so_rank = d;
     lt.lap("upload records, ranks");
     S.so_lb = nullptr; S.so_vis = nullptr;
     if (h->dfs_mode && h->cfg.force_generic == 0 && h->max_seq <= 256 && mto < 65535 && (long long)so_rec.size() * S.seq_pad * 5 <= (6ll << 30)) {
         // per sorted order, for the hybrid neighbour-search tick: its visit sequence (j-th visited cluster | orders of that cluster
         // of the same slot with a smaller id << 16) and, with byte costs, the cost bounds of those clusters (Static.lbc gathered
         // through the sequence once) - built ON THE DEVICE from the tables uploaded above (k_build_vis, vds_dfs.hip)
-        std::vector<int> so_bkt0(so_rec.size(), 0);
-        for_each_day(n_days, [&](int dd) {
-            const DayDesc &de = ddesc[dd];
-            for (int t = 0; t < de.T; ++t) {
-                const int b0 = de.bkt_base + t * C;
-                for (int q = bkt_off[b0]; q < bkt_off[b0 + C]; ++q) so_bkt0[q] = b0;
-            }
-        });
         int *d_b0;
-        if ((rc = upload(h, &d_b0, so_bkt0))) return rc;
+        if ((rc = upload(h, &d_b0, build_first_buckets(ot, nt)))) return rc;
         unsigned *dv;
         if ((rc = dev_alloc(h, &dv, so_rec.size() * (size_t)S.seq_pad))) return rc;
         unsigned char *dl = nullptr;
@@ -1436,130 +1059,36 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
     //      D.arr, in the order (destination cluster, earliest arrival slot a0, id); the destination bucket reads the slots of the
     //      orders that can arrive now instead of receiving atomically appended ring entries.
     S.so_slot = nullptr; S.d_rec = nullptr; S.d_first = nullptr; S.replica_desc2 = nullptr; S.pull_W = 0; S.pull_hmax = 0;
-    int Od_max = 0;
-    std::vector<int> d_first_keep;       // (one shared day: for the per-bucket descriptors below)
+    PullTables pt;
     if (S.pull) {
-        const int Hc = h->cfg.ring_ticks > 0 ? h->cfg.ring_ticks : 32;
-        const int tk = S.tick_minutes;
-        auto slots_of = [&](long long rel) -> int { return rel <= 0 ? 1 : (int)((rel + tk - 1) / tk); };      // post_arrival's d
-        pvec<int> so_slot(so_rec.size(), -1);
+        pvec<int> so_slot;
         pvec<int2> d_rec;
-        std::vector<int> d_first;
-        std::vector<int4> ddesc2(ddesc.size(), make_int4(0, 0, 0, 0));
-        int W = 0, hmax = 0;
-        bool ok = true;
-        // per day (in parallel, for_each_day): the day's pull orders in the order (destination cluster, earliest arrival slot a0, id) -
-        // a stable counting sort on (dc, a0) over the orders taken in id order (tick_off / ord_q); round 5: a comparison sort of
-        // 200 000 records was 14 of the 19 ms of a Reload at configs[1]
-        struct PullDay { std::vector<int> start; int npull = 0, W = 0, hmax = 0, TA = 0, code = 0; };
-        std::vector<PullDay> PD(n_days);
-        auto for_pull = [&](const DayDesc &de, auto &&fn) {
-            for (int t = 0; t < de.T; ++t)
-                for (int ix = tick_off[de.tick_base + t]; ix < tick_off[de.tick_base + t + 1]; ++ix) {
-                    const int q = ord_q[ix];
-                    const int4 &rr = so_rec[q];
-                    const int c = (int)((unsigned)rr.z >> 16);
-                    const int dmin = slots_of(rr.w), dmax = slots_of((long long)rr.w + h->cl_cmax[c]);
-                    if (dmax >= Hc) continue;            // may outlive the ring horizon: stays on the ring / far path
-                    fn(q, rr, t, dmin, dmax);
-                }
-        };
-        for (int dd = 0; dd < n_days; ++dd) { PD[dd].TA = ddesc[dd].T + Hc; if (PD[dd].TA >= 65535) ok = false; }      // a0 < T + H for every pull order
-        if (ok) for_each_day(n_days, [&](int dd) {
-            PullDay &P = PD[dd];
-            try {
-                const int TA = P.TA;
-                P.start.assign((size_t)C * (TA + 1) + 1, 0);
-                for_pull(ddesc[dd], [&](int, const int4 &rr, int t, int dmin, int dmax) {
-                    P.W = std::max(P.W, dmax - dmin);
-                    P.hmax = std::max(P.hmax, dmin);
-                    P.start[(size_t)(rr.z & 0xFFFF) * (TA + 1) + (t + dmin) + 1]++;
-                    ++P.npull;
-                });
-                for (size_t kx = 0; kx + 1 < P.start.size(); ++kx) P.start[kx + 1] += P.start[kx];
-            } catch (...) { P.code = VDS_ENOMEM; }
-        });
-        std::vector<size_t> rbase(n_days + 1, 0), fbase(n_days + 1, 0);
-        for (int dd = 0; dd < n_days && ok; ++dd) {
-            if (PD[dd].code) return fail(h, VDS_ENOMEM, "vds_load_orders: out of host memory");
-            rbase[dd + 1] = rbase[dd] + (size_t)PD[dd].npull;
-            fbase[dd + 1] = fbase[dd] + (size_t)(PD[dd].TA + 1) * C;
-            W = std::max(W, PD[dd].W); hmax = std::max(hmax, PD[dd].hmax); Od_max = std::max(Od_max, PD[dd].npull);
-            ddesc2[dd] = make_int4((int)fbase[dd], (int)rbase[dd], PD[dd].TA, PD[dd].npull);
-        }
-        if (fbase[n_days] >= (1ull << 31) || rbase[n_days] >= (1ull << 31)) ok = false;
-        if (ok) {
-            d_rec.resize(rbase[n_days]);
-            d_first.resize(fbase[n_days]);
-            for_each_day(n_days, [&](int dd) {
-                PullDay &P = PD[dd];
-                const int TA = P.TA, base = (int)rbase[dd];
-                // d_first[a][c]: first position (absolute) of the day's orders to cluster c with a0 >= a, a = 0 .. TA
-                int *first = d_first.data() + fbase[dd];
-                for (int c = 0; c < C; ++c)
-                    for (int a = 0; a <= TA; ++a) first[(size_t)a * C + c] = base + P.start[(size_t)c * (TA + 1) + a];
-                for_pull(ddesc[dd], [&](int q, const int4 &rr, int t, int dmin, int) {
-                    const int a0 = t + dmin;
-                    const int i = P.start[(size_t)(rr.z & 0xFFFF) * (TA + 1) + a0]++;
-                    d_rec[(size_t)base + i] = make_int2((int)dense_key(t, 0, rr.x), a0 | ((int)((unsigned)rr.y >> 16) << 16) | (dmin << 24));
-                    so_slot[q] = i;
-                });
-            });
-        }
-        if ((long long)d_first.size() >= (1ll << 31) || W > DENSE_PULL_WMAX) ok = false;
-        if (ok && S.dense_st)               // (stamp form: every processed order owns a slot)
-            for (int dd = 0; dd < n_days; ++dd) ok = ok && PD[dd].npull == ddesc[dd].Oq;
-        if (!ok && S.dense_st) { S.dense = 0; S.dense_st = 0; }              // neighbour search keeps the wide layout (hybrid tick on k_tick_rows)
-        if (!ok) S.pull = 0;
+        if ((rc = build_pull_tables(ot, city, ring_H, S.dense_st != 0, nt, [&](size_t n) { so_slot.resize(n); return so_slot.data(); },
+                                    [&](size_t n) { d_rec.resize(n); return d_rec.data(); }, pt, msg)))
+            return fail(h, rc, "%s", msg.c_str());
+        if (!pt.ok && S.dense_st) { S.dense = 0; S.dense_st = 0; }           // neighbour search keeps the wide layout (hybrid tick on k_tick_rows)
+        if (!pt.ok) S.pull = 0;
         else {
-            struct Sink2 { vds_handle *h; ~Sink2() { h->alloc_sink = nullptr; } } sink2{h};
-            h->alloc_sink = &h->order_allocs;
-            S.pull_W = W; S.pull_hmax = hmax;
+            S.pull_W = pt.W; S.pull_hmax = pt.hmax;
             if ((rc = upload(h, &d, so_slot))) return rc; S.so_slot = d;
             int2 *d2; if ((rc = upload(h, &d2, d_rec))) return rc; S.d_rec = d2;
-            if ((rc = upload(h, &d, d_first))) return rc; S.d_first = d;
-            h->pull_desc = ddesc2;
-            d_first_keep = d_first;
+            if ((rc = upload(h, &d, pt.d_first))) return rc; S.d_first = d;
+            h->pull_desc = pt.ddesc2;
             h->pull_drec = std::move(d_rec);          // (uploaded above; not read again below: a 25 MB copy at 16 days)
-            h->pull_slot_q.assign(h->pull_drec.size(), 0);
-            for_each_day(n_days, [&](int dd) {
-                const int qb = ddesc[dd].q_base;
-                for (int q = qb; q < qb + ddesc[dd].Oq; ++q)
-                    if (so_slot[q] >= 0) h->pull_slot_q[(size_t)ddesc2[dd].y + so_slot[q]] = q - qb;
-            });
+            build_slot_orders(ot, pt, nt, h->pull_slot_q);
         }
     }
-    h->pull_Od_max = Od_max;
+    h->pull_Od_max = pt.Od_max;
     lt.lap("static arrival slots");
     // per-bucket descriptors of the dense tick with one shared day (Static.tdesc)
     S.tdesc = nullptr;
     if (S.dense && n_days == 1 && (int)h->corder_host.size() == C) {
-        const DayDesc &de = ddesc[0];
-        // 32 bytes per (slot, cluster): the bucket's descriptor, then the cluster's (Static.cdesc_dense[ci]) - one scalar load
-        std::vector<int4> td((size_t)std::max(de.T, 1) * C * 2, make_int4(0, 0, 0, 0));
-        std::vector<int4> cdd((size_t)C);
-        HIPCHK(h, hipMemcpy(cdd.data(), S.cdesc_dense, (size_t)C * sizeof(int4), hipMemcpyDeviceToHost));
-        for (int t = 0; t < de.T; ++t)
-            for (int ci = 0; ci < C; ++ci) {
-                const int c = h->corder_host[ci];
-                const int q0 = bkt_off[de.bkt_base + (size_t)t * C + c], k = bkt_off[de.bkt_base + (size_t)t * C + c + 1] - q0;
-                int clo = 0, n = 0;
-                if (S.pull) {
-                    clo = d_first_keep[(size_t)std::max(t - S.pull_W, 0) * C + c];
-                    n = d_first_keep[(size_t)(t + 1) * C + c] - clo;
-                }
-                td[2 * ((size_t)t * C + ci)] = make_int4(q0, k, clo, n);
-                td[2 * ((size_t)t * C + ci) + 1] = cdd[ci];
-            }
-        struct Sink3 { vds_handle *h; ~Sink3() { h->alloc_sink = nullptr; } } sink3{h};
-        h->alloc_sink = &h->order_allocs;
-        int4 *dtd; if ((rc = upload(h, &dtd, td))) return rc; S.tdesc = dtd;
+        int4 *dtd; if ((rc = upload(h, &dtd, build_bucket_descs(ot, h->corder_host, h->cdesc_dense_host, S.pull ? &pt : nullptr)))) return rc; S.tdesc = dtd;
     }
-    h->alloc_sink = nullptr;
     lt.lap("bucket descriptors");
+    into.reset();                                       // (the order tables end here)
     if ((rc = apply_replica_map(h))) return rc;         // S.R (stored replicas), S.T, the map's arrays
-    h->alloc_sink = nullptr;
-    h->alloc_O = (int)std::min<long long>(Ototal / n_days, 0x7fffffff);
+    h->alloc_O = (int)std::min<long long>(ot.Ototal / n_days, 0x7fffffff);
     if ((rc = alloc_state(h, h->alloc_O))) return rc;
     lt.lap("state tables");
     {   // preconditions of k_tick_replica2 (packed ids, 16-bit positions / nodes / costs, LDS footprint)
@@ -2506,8 +2035,7 @@ int vds_supply_inplace(vds_handle *h, void **ring, int64_t *stride_plane, int64_
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->want_sup = true;
         int rc;
-        struct Sink { vds_handle *h; std::vector<void *> *old; ~Sink() { h->alloc_sink = old; } } sink{h, h->alloc_sink};
-        h->alloc_sink = &h->state_allocs;
+        AllocInto into(h, &h->state_allocs);
         if ((rc = dev_alloc(h, &h->D.sup, (size_t)VDS_SUP_PLANES * h->S.C * h->S.R)) || (rc = dev_alloc(h, &h->D.sup_slot, (size_t)1))) { h->D.sup = nullptr; h->D.sup_slot = nullptr; return rc; }
         HIPCHK(h, hipMemsetAsync(h->D.sup, 0, (size_t)VDS_SUP_PLANES * h->S.C * h->S.R * sizeof(int), h->stream));
         HIPCHK(h, hipMemsetAsync(h->D.sup_slot, 0, sizeof(int), h->stream));
@@ -2533,8 +2061,7 @@ int vds_counters_device(vds_handle *h, void **dev_ptr) {
 // int64 [4][R_ext][C] block, made on the first request (it lives with the state tables: re-made when they are).
 static int ensure_outcomes(vds_handle *h) {
     if (h->d_outc) return VDS_OK;
-    struct Sink { vds_handle *h; std::vector<void *> *old; ~Sink() { h->alloc_sink = old; } } sink{h, h->alloc_sink};
-    h->alloc_sink = &h->state_allocs;
+    AllocInto into(h, &h->state_allocs);
     const size_t n = 4 * (size_t)h->R_ext * h->S.C;
     const int rc = dev_alloc(h, &h->d_outc, n);
     if (rc) { h->d_outc = nullptr; return rc; }
@@ -2584,8 +2111,7 @@ static int ensure_idle_heads(vds_handle *h, int L) {
         dev_free(h->d_heads);
         h->d_heads = nullptr; h->heads_L = 0;
     }
-    struct Sink { vds_handle *h; std::vector<void *> *old; ~Sink() { h->alloc_sink = old; } } sink{h, h->alloc_sink};
-    h->alloc_sink = &h->state_allocs;
+    AllocInto into(h, &h->state_allocs);
     const size_t n = 2 * (size_t)h->R_ext * h->S.C * L;
     const int rc = dev_alloc(h, &h->d_heads, n);
     if (rc) { h->d_heads = nullptr; return rc; }
