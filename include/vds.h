@@ -356,6 +356,37 @@ int vds_read_idle_heads(vds_handle *h, int32_t L, int32_t *veh, int32_t *node);
  * launched.  L outside 0 .. VDS_IDLE_HEADS_MAX: VDS_EINVAL.  A parameter of its own, not a bit of `planes` (which stays 0 .. 63). */
 int vds_run_hooked_idle_heads(vds_handle *h, int32_t L);
 
+/* Snapshot and restore of the episode state, with per-replica forking (no reference counterpart: a Simulation cannot go back; the
+ * nearest thing is Reload + replaying the day, simulator.py:130-212, :1048-1091).
+ * vds_snapshot saves the episode state of every replica as it stands: the idle lists, the vehicles on their way (arrival ring, far
+ * tables, static arrival slots), the counters, the per-order results, the supply planes and the clock (self.step, whether that slot
+ * has been stepped, the dispatch sequence numbers).  Valid after any vds_reset*: between slots (after a reset or vds_advance) or
+ * inside a slot (after vds_step, before or after that slot's dispatch calls, before vds_advance - where a policy branches).
+ * Asynchronous on the handle's stream.  A handle holds ONE snapshot, a second call overwrites it; its storage is allocated by the
+ * first call (the only point that may synchronise), sized like the tables it mirrors - a handle that never takes one allocates
+ * nothing.  It survives later vds_reset*, vds_step, vds_run*, dispatch calls and vds_set_run_groups; it is VOID after whatever re-makes
+ * the state or result tables or changes their strides: vds_load_orders*, vds_set_replica_days, a vds_set_idle_cap that replaces the idle tables (also the
+ * one a vds_reset issues to regrow them), the first vds_supply_inplace, the whole-day change of k_tick_dense's base form.
+ * vds_restore makes replica r (the caller's index) continue from the snapshot's replica src_replica[r] - [replicas] host values, not
+ * retained; NULL: every replica from itself, the plain rollback.  Afterwards every read entry point (vds_read_obs and the device
+ * planes, vds_read_counters, vds_read_orders, vds_read_lists, vds_read_vehicles, vds_read_outcomes, vds_read_idle_heads, vds_clock)
+ * answers as it did at the snapshot with replica r showing src_replica[r]'s values, and vds_step / vds_run / vds_run_hooked continue
+ * from the restored slot.  Asynchronous.  A snapshot can be restored any number of times.  VDS_ESTATE "no snapshot" when there is
+ * none or it is void; VDS_EINVAL for a map entry outside [0, replicas); VDS_EINVAL with order days per replica when replica r and
+ * src_replica[r] replay different days (a replica can only continue on the day it replays).
+ * vds_restore_device: the same from a DEVICE-resident map, int32 [replicas] - nothing crosses PCIe when a torch policy computed the
+ * selection; the handle's stream must be ordered after its producer.  VDS_ESTATE when more than one order day is resident (the host
+ * cannot check the days).  An entry outside [0, replicas) leaves that replica on its own snapshot row and raises a sticky error
+ * that the next vds_sync / vds_read_* reports once (VDS_ESTATE), as for a refused vds_apply_dispatch_device action.
+ * vds_snapshot_info: the snapshot's slot (*step), whether that slot had been stepped (*stepped: 1 / 0) and the bytes of device memory
+ * the store holds; any pointer may be NULL; VDS_ESTATE when there is no (valid) snapshot.
+ * vds_snapshot_drop frees the store (synchronises the handle's stream if there is one). */
+int vds_snapshot(vds_handle *h);
+int vds_restore(vds_handle *h, const int32_t *src_replica);
+int vds_restore_device(vds_handle *h, const void *dev_src_replica);
+int vds_snapshot_info(const vds_handle *h, int32_t *step, int32_t *stepped, int64_t *bytes);
+int vds_snapshot_drop(vds_handle *h);
+
 /* As vds_reduce_counters, delivering the int64 [VDS_NUM_COUNTERS] totals of this handle's
  * replicas (raw device sums; VALUE_SUM = matched orders only) into caller-owned DEVICE memory,
  * asynchronously on the handle's stream - the send buffer of the cross-GPU RCCL all-reduce. */

@@ -81,6 +81,11 @@ SYMBOLS = {
     "vds_idle_heads_device": (C.c_int, [_VP, _I32, C.POINTER(_VP)]),
     "vds_read_idle_heads": (C.c_int, [_VP, _I32, _VP, _VP]),
     "vds_run_hooked_idle_heads": (C.c_int, [_VP, _I32]),
+    "vds_snapshot": (C.c_int, [_VP]),
+    "vds_restore": (C.c_int, [_VP, _VP]),
+    "vds_restore_device": (C.c_int, [_VP, _VP]),
+    "vds_snapshot_info": (C.c_int, [_VP, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64)]),
+    "vds_snapshot_drop": (C.c_int, [_VP]),
     "vds_read_counters": (C.c_int, [_VP, _VP]),
     "vds_reduce_counters": (C.c_int, [_VP, _VP, C.POINTER(_VP)]),
     "vds_reduce_counters_into": (C.c_int, [_VP, _VP]),

@@ -223,6 +223,30 @@ struct vds_handle {
     const void *hook_actions = nullptr;
     void *hook_policy = nullptr;
     hipStream_t hook_stream = nullptr;
+    // vds_snapshot / vds_restore: ONE saved episode state per handle - a store sized like the state and result tables it mirrors, made
+    // on the first vds_snapshot (a handle that never takes one allocates nothing), and the host's part of the state: the clock
+    unsigned state_gen = 0;                  // bumped wherever the state / result tables are re-made or their meaning changes (another day, another
+                                             // map, other capacities, the supply planes switched on, the base form of the whole-day rule): a
+                                             // snapshot taken before is void.  (Not tables_gen: that one also moves with the run groups and the
+                                             // per-slot forms, which leave the tables alone - a snapshot outlives them as it outlives a reset.)
+    struct Snap {
+        State D{};                           // the store: hdr, cnt, idle, ring, ring_min, ring_cnt, fl, inbox, sup, arr, out (the rest stays null)
+        std::vector<void *> allocs;
+        long long bytes = 0;
+        bool valid = false;
+        unsigned gen = 0;                    // state_gen and the capacities the store was made for / the snapshot taken under
+        int R = 0, C = 0, idle_cap = 0, ring_cap = 0, fl_cap = 0, H = 0, dense = 0, Oq = 0, arr_slots = 0;
+        bool sup = false, arr = false;
+        int t = 0, last_stepped = -1, dispatch_seq = 0, seq_tick0 = 0, seq_tick = -1;
+        int *d_map = nullptr;                // [R] the restore map in stored replica indices (host maps are uploaded here, device maps checked into it)
+        // host maps are staged in two alternating pinned buffers, each guarded by an event recorded behind its upload: vds_restore waits
+        // only for the upload of the restore before the last one, which has long finished - the call stays asynchronous
+        int *pin_map[2] = {nullptr, nullptr};
+        hipEvent_t pin_ev[2] = {nullptr, nullptr};
+        bool pin_used[2] = {false, false};
+        int pin_i = 0;
+    } snap;
+    bool restored_episode = false;           // the episode continues from a snapshot: its slow-path statistics describe no whole day (adapt_dense)
 };
 
 static int fail(vds_handle *h, int code, const char *fmt, ...) {
@@ -622,6 +646,11 @@ int vds_destroy(vds_handle *h) {
     for (void *p : h->result_allocs) dev_free(p);
     for (void *p : h->state_allocs) dev_free(p);
     for (void *p : h->idle_allocs) dev_free(p);
+    for (void *p : h->snap.allocs) dev_free(p);
+    for (int i = 0; i < 2; ++i) {
+        if (h->snap.pin_map[i]) (void)hipHostFree(h->snap.pin_map[i]);
+        if (h->snap.pin_ev[i]) (void)hipEventDestroy(h->snap.pin_ev[i]);
+    }
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     drop_run_graph(h);
     if (h->forms.ev) (void)hipEventDestroy(h->forms.ev);
@@ -927,7 +956,7 @@ static int set_replica_days_impl(vds_handle *h, const int32_t *replica_day) {
         if ((rc = alloc_state(h, h->alloc_O))) return rc;
         if ((rc = alloc_results(h))) return rc;
     }
-    { h->run_stale = true; h->tables_gen++; }
+    { h->run_stale = true; h->tables_gen++; h->state_gen++; }
     h->have_reset = false;                              // the episode state belongs to the previous map: vds_reset* must follow
     h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1;
     return VDS_OK;
@@ -951,7 +980,7 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
             else dev_free(p);
         }
         h->order_allocs.clear();
-        { h->run_stale = true; h->tables_gen++; }
+        { h->run_stale = true; h->tables_gen++; h->state_gen++; }
         h->have_orders = false; h->have_reset = false;
         h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1;
         h->err.clear();
@@ -1263,6 +1292,7 @@ static bool request_counters(vds_handle *h) {
         *f.pin_slow = 0;
     }
     if (!h->have_reset || h->t <= 0) return true;
+    if (h->restored_episode) return true;               // (slots re-run behind a restore: the counts describe no whole day - the last request stands)
     f.ticks_valid = false;
     const bool ok = hipMemcpyAsync(f.pin_slow, h->D.err + 2, sizeof(int), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
     if (ok && h->D.slow_tick && h->t == S.T && S.T > 0 && S.T <= h->slow_tick_cap && S.C == h->slow_tick_C) {
@@ -1337,6 +1367,7 @@ static void adapt_dense(vds_handle *h) {
             S.dense_lpr = 16; S.dense_tab = (t256 && *t256 == '0') ? 128 : 256;
             f.adapt = 1;
             h->run_stale = true; h->tables_gen++;               // the day graph holds the other kernel
+            h->state_gen++;                                     // (and a snapshot belongs to the base form it was taken under)
             return;
         }
     }
@@ -1389,6 +1420,7 @@ static int reset_device(vds_handle *h) {
     }
     HIPCHK(h, hipGetLastError());
     h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1;
+    h->restored_episode = false;
     h->have_reset = true; h->nodes_valid = true;
     return VDS_OK;
 }
@@ -1405,6 +1437,7 @@ static int set_idle_cap_impl(vds_handle *h, int32_t cap) {
     if (cap > (1 << 24)) return fail(h, VDS_EINVAL, "vds_set_idle_cap: %d > 2^24 unsupported", cap);
     if (cap == h->S.idle_cap) return VDS_OK;
     if (h->S.dense_st && cap > 16384) return fail(h, VDS_ECAPACITY, "vds_set_idle_cap: neighbour search on the dense layout holds at most 16384 entries per list (VDS_DENSE_DFS=0 keeps the wide layout)");
+    h->state_gen++;                                     // (the idle tables are replaced: a snapshot of the old ones is void)
     for (void *p : h->idle_allocs) dev_free(p);
     h->idle_allocs.clear();
     h->alloc_sink = &h->idle_allocs;
@@ -1888,6 +1921,170 @@ int vds_sync(vds_handle *h) {
         HIPCHK(h, hipMemcpy(h->D.err, &keep, sizeof(int), hipMemcpyHostToDevice));
         return fail(h, VDS_ESTATE, "dispatch of an idle position that does not exist (or listed twice); the action was skipped");
     }
+    if (err[0] & ERR_RESTORE) {
+        // the replica kept its own snapshot row, every other one was restored: consistent - reported once and cleared, like a refused dispatch
+        const int keep = err[0] & ~ERR_RESTORE;
+        HIPCHK(h, hipMemcpy(h->D.err, &keep, sizeof(int), hipMemcpyHostToDevice));
+        return fail(h, VDS_ESTATE, "vds_restore_device: a map entry outside [0, %d) replicas; that replica was restored from its own snapshot row", h->R_ext);
+    }
+    return VDS_OK;
+}
+
+// ---- vds_snapshot / vds_restore: the episode state of every replica saved in a store next to the tables and copied back through a
+// replica map (vds_snapshot.hip).  What is saved: hdr, cnt, idle, ring, ring_min, ring_cnt, fl, both inbox parities, sup, arr, out and the
+// clock (t, last_stepped, the dispatch sequence numbers).  What is not: work / slog / dry (consumed or cleared inside the slot's own
+// launches), err / slow_tick / sup_slot (rewritten by every tick launch; the slot word is set to the restored slot's), the derived
+// blocks (d_obs, d_outc, d_heads, d_cnt_*) and stamp (every stamp is 0xFFFF between API calls: the lists are compact there).
+static void snap_free(vds_handle *h) {
+    vds_handle::Snap &s = h->snap;
+    if (!s.allocs.empty()) (void)hipStreamSynchronize(h->stream);           // (a copy may still be running)
+    for (void *p : s.allocs) dev_free(p);
+    s.allocs.clear();
+    for (int i = 0; i < 2; ++i) {
+        if (s.pin_map[i]) (void)hipHostFree(s.pin_map[i]);
+        if (s.pin_ev[i]) (void)hipEventDestroy(s.pin_ev[i]);
+        s.pin_map[i] = nullptr; s.pin_ev[i] = nullptr; s.pin_used[i] = false;
+    }
+    s.D = State{}; s.d_map = nullptr; s.bytes = 0; s.valid = false;
+}
+// the store fits the tables as they stand
+static bool snap_fits(const vds_handle *h) {
+    const vds_handle::Snap &s = h->snap;
+    const Static &S = h->S;
+    return !s.allocs.empty() && s.gen == h->state_gen && s.R == S.R && s.C == S.C && s.idle_cap == S.idle_cap && s.ring_cap == S.ring_cap && s.fl_cap == S.fl_cap &&
+           s.H == S.H && s.dense == S.dense && s.Oq == S.Oq && s.arr_slots == S.arr_slots && s.sup == (h->D.sup != nullptr) && s.arr == (S.pull && h->D.arr != nullptr);
+}
+static int snap_alloc(vds_handle *h) {
+    snap_free(h);
+    vds_handle::Snap &s = h->snap;
+    const Static &S = h->S;
+    const State &D = h->D;
+    const size_t B = (size_t)S.C * S.R, HB = (size_t)S.H * B;
+    s.gen = h->state_gen; s.R = S.R; s.C = S.C; s.idle_cap = S.idle_cap; s.ring_cap = S.ring_cap; s.fl_cap = S.fl_cap; s.H = S.H; s.dense = S.dense;
+    s.Oq = S.Oq; s.arr_slots = S.arr_slots; s.sup = D.sup != nullptr; s.arr = S.pull && D.arr != nullptr;
+    AllocInto into(h, &s.allocs);
+    size_t bytes = 0;
+    auto get = [&](auto **p, size_t n) { const int rc = dev_alloc(h, p, n); if (!rc) bytes += std::max<size_t>(n, 1) * sizeof(**p); return rc; };
+    int rc;
+    // (sized like alloc_state / alloc_results size the tables they mirror)
+    if ((rc = get(&s.D.hdr, B * HDR_WORDS)) || (rc = get(&s.D.cnt, B * CNT_WORDS)) ||
+        (rc = get(&s.D.idle, S.dense ? (B * S.idle_cap + 1) / 2 : B * S.idle_cap)) ||
+        (rc = get(&s.D.ring, S.dense ? (HB * S.ring_cap + 1) / 2 : HB * S.ring_cap)) ||
+        (D.ring_min && (rc = get(&s.D.ring_min, HB * S.ring_cap))) ||
+        (rc = get(&s.D.ring_cnt, HB)) || (rc = get(&s.D.fl, B * S.fl_cap)) || (rc = get(&s.D.inbox, 2 * B * S.in_cap)) ||
+        (s.sup && (rc = get(&s.D.sup, (size_t)VDS_SUP_PLANES * B))) ||
+        (s.arr && (rc = get(&s.D.arr, (size_t)S.R * S.arr_slots))) ||
+        (rc = get(&s.D.out, (size_t)S.R * std::max(S.Oq, 1))) || (rc = get(&s.d_map, (size_t)S.R))) {
+        const std::string msg = h->err;
+        snap_free(h);
+        h->err = msg;
+        return rc;
+    }
+    for (int i = 0; i < 2; ++i)
+        if (hipHostMalloc((void **)&s.pin_map[i], (size_t)S.R * sizeof(int), hipHostMallocDefault) != hipSuccess ||
+            hipEventCreateWithFlags(&s.pin_ev[i], hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            snap_free(h);
+            return fail(h, VDS_ENOMEM, "vds_snapshot: no pinned host memory for the restore map");
+        }
+    s.bytes = (long long)bytes;
+    return VDS_OK;
+}
+// every table of the snapshot, src -> dst, on the handle's stream
+static int snap_copy(vds_handle *h, const State &src, const State &dst, const int *map, int tdone) {
+    Chain c(h->stream);
+    for (int tb = 0; tb < SNAP_TABLES; ++tb) c.add(emit_snap_table, h->S, src, dst, map, tb, tdone);
+    HIPCHK(h, hipGetLastError());
+    return VDS_OK;
+}
+
+static int snapshot_impl(vds_handle *h) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_snapshot: call vds_reset first");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    vds_handle::Snap &s = h->snap;
+    s.valid = false;
+    if (!snap_fits(h)) { const int rc = snap_alloc(h); if (rc) return rc; }
+    const int rc = snap_copy(h, h->D, s.D, nullptr, h->last_stepped + 1);
+    if (rc) return rc;
+    s.t = h->t; s.last_stepped = h->last_stepped; s.dispatch_seq = h->dispatch_seq; s.seq_tick0 = h->seq_tick0; s.seq_tick = h->seq_tick;
+    s.valid = true;
+    return VDS_OK;
+}
+
+// the copies and the clock of a restore; map: null (identity) or the handle's device map, filled by the caller
+static int restore_finish(vds_handle *h, const int *user_dev_map, const int *map) {
+    vds_handle::Snap &s = h->snap;
+    const Static &S = h->S;
+    if (user_dev_map || h->D.sup_slot) {     // (a device map to check, a slot word to set: otherwise the kernel has nothing to do)
+        Chain c(h->stream);
+        c.add(emit_snap_prep, user_dev_map, s.d_map, S.R, h->D.err, h->D.sup_slot, s.last_stepped < 0 ? 0 : (s.last_stepped + 1) & (VDS_SUP_PLANES - 1));
+    }
+    const int rc = snap_copy(h, s.D, h->D, map, s.last_stepped + 1);
+    if (rc) return rc;
+    h->t = s.t; h->last_stepped = s.last_stepped; h->dispatch_seq = s.dispatch_seq; h->seq_tick0 = s.seq_tick0; h->seq_tick = s.seq_tick;
+    h->restored_episode = true;
+    return VDS_OK;
+}
+static int restore_check(vds_handle *h, const char *who) {
+    if (!h) return VDS_EINVAL;
+    if (!h->snap.valid || !snap_fits(h)) {
+        if (h->snap.valid) { h->snap.valid = false; snap_free(h); }     // (void: the tables were re-made since; the store goes)
+        return fail(h, VDS_ESTATE, "%s: no snapshot (none taken, or the state tables were re-made since: vds_load_orders*, vds_set_replica_days, vds_set_idle_cap, a reset that regrew the idle tables, vds_supply_inplace)", who);
+    }
+    if (!h->have_reset) return fail(h, VDS_EINVAL, "%s: call vds_reset first", who);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return VDS_OK;
+}
+static int restore_impl(vds_handle *h, const int32_t *src_replica) {
+    int rc = restore_check(h, "vds_restore");
+    if (rc) return rc;
+    if (!src_replica) return restore_finish(h, nullptr, nullptr);
+    const Static &S = h->S;
+    vds_handle::Snap &s = h->snap;
+    for (int r = 0; r < h->R_ext; ++r) {
+        const int m = src_replica[r];
+        if (m < 0 || m >= h->R_ext) return fail(h, VDS_EINVAL, "vds_restore: replica %d is mapped to replica %d of %d", r, m, h->R_ext);
+        if (h->replica_day[r] != h->replica_day[m])
+            return fail(h, VDS_EINVAL, "vds_restore: order days per replica: replica %d replays day %d, replica %d day %d - a replica can only continue on the day it replays", r, h->replica_day[r], m, h->replica_day[m]);
+    }
+    // stored replica indices (regrouped storage: through ext2int; a padding replica maps to itself)
+    const int pi = s.pin_i;
+    s.pin_i ^= 1;
+    if (s.pin_used[pi]) HIPCHK(h, hipEventSynchronize(s.pin_ev[pi]));          // (the upload this buffer was the source of, two restores ago)
+    int *stage = s.pin_map[pi];
+    for (int ri = 0; ri < S.R; ++ri) {
+        const int re = h->int2ext.empty() ? ri : h->int2ext[ri];
+        stage[ri] = re < 0 ? ri : (h->ext2int.empty() ? src_replica[re] : h->ext2int[src_replica[re]]);
+    }
+    HIPCHK(h, hipMemcpyAsync(s.d_map, stage, (size_t)S.R * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(s.pin_ev[pi], h->stream));
+    s.pin_used[pi] = true;
+    return restore_finish(h, nullptr, s.d_map);
+}
+static int restore_device_impl(vds_handle *h, const void *dev_src_replica) {
+    int rc = restore_check(h, "vds_restore_device");
+    if (rc) return rc;
+    if (!dev_src_replica) return fail(h, VDS_EINVAL, "vds_restore_device: null map (vds_restore(h, NULL) is the plain rollback)");
+    if (h->S.n_days > 1 || !h->int2ext.empty() || h->S.R != h->R_ext)
+        return fail(h, VDS_ESTATE, "vds_restore_device: order days per replica: the host cannot check that a replica continues on the day it replays - use vds_restore");
+    return restore_finish(h, (const int *)dev_src_replica, h->snap.d_map);
+}
+
+int vds_snapshot(vds_handle *h) { return guarded(h, "vds_snapshot", [&] { return snapshot_impl(h); }); }
+int vds_restore(vds_handle *h, const int32_t *src_replica) { return guarded(h, "vds_restore", [&] { return restore_impl(h, src_replica); }); }
+int vds_restore_device(vds_handle *h, const void *dev_src_replica) { return guarded(h, "vds_restore_device", [&] { return restore_device_impl(h, dev_src_replica); }); }
+int vds_snapshot_info(const vds_handle *h, int32_t *step, int32_t *stepped, int64_t *bytes) {
+    if (!h) return VDS_EINVAL;
+    if (!h->snap.valid || !snap_fits(h)) return VDS_ESTATE;
+    if (step) *step = h->snap.t;
+    if (stepped) *stepped = h->snap.last_stepped == h->snap.t;
+    if (bytes) *bytes = h->snap.bytes;
+    return VDS_OK;
+}
+int vds_snapshot_drop(vds_handle *h) {
+    if (!h) return VDS_EINVAL;
+    (void)hipSetDevice(h->cfg.device);
+    snap_free(h);
     return VDS_OK;
 }
 
@@ -2039,7 +2236,7 @@ int vds_supply_inplace(vds_handle *h, void **ring, int64_t *stride_plane, int64_
         if ((rc = dev_alloc(h, &h->D.sup, (size_t)VDS_SUP_PLANES * h->S.C * h->S.R)) || (rc = dev_alloc(h, &h->D.sup_slot, (size_t)1))) { h->D.sup = nullptr; h->D.sup_slot = nullptr; return rc; }
         HIPCHK(h, hipMemsetAsync(h->D.sup, 0, (size_t)VDS_SUP_PLANES * h->S.C * h->S.R * sizeof(int), h->stream));
         HIPCHK(h, hipMemsetAsync(h->D.sup_slot, 0, sizeof(int), h->stream));
-        { h->run_stale = true; h->tables_gen++; }
+        { h->run_stale = true; h->tables_gen++; h->state_gen++; }
         h->have_reset = false;                      // vds_reset / vds_reset_again / vds_reset_random must follow
         h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1;
     }

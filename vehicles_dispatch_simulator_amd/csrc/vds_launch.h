@@ -55,4 +55,13 @@ void launch_slot_outcomes(const Static &S, const State &D, int t, int stepped, l
 // ---- vds_idle_heads.hip
 void emit_idle_heads(const Emit &e, const Static &S, const State &D, int L, int *heads, int r_lo, int r_n);
 void launch_idle_heads(const Static &S, const State &D, int L, int *heads, hipStream_t st);
+// ---- vds_snapshot.hip
+// the tables of a snapshot, one launch each: `src` -> `dst` are State views of the live tables and of the store (either way round),
+// map [S.R] stored replica -> stored source replica (null: identity), tdone the slots whose orders have been processed (SNAP_OUT)
+enum { SNAP_HDR, SNAP_CNT, SNAP_IDLE, SNAP_RING, SNAP_RING_MIN, SNAP_RING_CNT, SNAP_FL, SNAP_INBOX, SNAP_SUP, SNAP_ARR, SNAP_OUT, SNAP_TABLES };
+void emit_snap_table(const Emit &e, const Static &S, const State &src, const State &dst, const int *map, int table, int tdone);
+// sticky device error bit (err[0], next to the ERR_* of vds_device.h): a device-resident restore map named a replica outside [0, R)
+enum { ERR_RESTORE = 32 };
+// the caller's device map `user` (null: none) checked into `map`; the supply planes' slot word (nullable) set to sup_val
+void emit_snap_prep(const Emit &e, const int *user, int *map, int R, int *err, int *sup_slot, int sup_val);
 }  // namespace vds

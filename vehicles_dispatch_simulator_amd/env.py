@@ -227,6 +227,47 @@ class BatchedDispatchEnv:
     def advance(self):
         self._chk(self._lib.vds_advance(self._h))
 
+    # -- snapshot / restore ---------------------------------------------------------------
+    def snapshot(self):
+        """Save the episode state of every replica as it stands (``vds_snapshot``; asynchronous): between slots, or inside a slot after
+        ``step`` - before or after that slot's dispatch calls - where a policy branches.  One snapshot per env, a second call
+        overwrites it; it outlives ``reset*`` / ``step`` / ``run*`` and is void after ``load_orders*``, ``set_replica_days``,
+        ``set_idle_cap`` (anything that re-makes the state tables)."""
+        self._chk(self._lib.vds_snapshot(self._h))
+
+    def restore(self, src=None):
+        """Replica ``r`` continues from the snapshot's replica ``src[r]`` (``vds_restore``; asynchronous); ``src``: int array-like
+        ``[R]``, ``None`` = every replica from itself (rollback).  Clock, lists, counters, results read as at the snapshot;
+        ``step`` / ``run`` / ``run_hooked`` go on from the restored slot.  With order days per replica ``r`` and ``src[r]`` must replay
+        the same day."""
+        if src is None:
+            self._chk(self._lib.vds_restore(self._h, None))
+            return
+        m = _i32(src).reshape(-1)
+        if m.size != self.R:
+            raise Exception("restore: expected %d source replicas, got %d" % (self.R, m.size))
+        self._chk(self._lib.vds_restore(self._h, _p(m)))
+
+    def restore_torch(self, src):
+        """``restore`` from a device-resident map (``vds_restore_device``): ``src`` a contiguous int32 CUDA tensor ``[R]``, produced on
+        (or synchronised with) the handle's stream and alive until the stream has passed the call.  An entry outside ``[0, R)`` leaves
+        that replica on its own snapshot row; the next ``sync`` / read raises once.  Raises with order days per replica."""
+        if tuple(src.shape) != (self.R,) or str(src.dtype) != "torch.int32" or not src.is_cuda or not src.is_contiguous():
+            raise Exception("restore_torch: expected a contiguous int32 CUDA tensor [R]")
+        self._chk(self._lib.vds_restore_device(self._h, C.c_void_p(src.data_ptr())))
+
+    def snapshot_info(self) -> Optional[Dict[str, int]]:
+        """``{step, stepped, bytes}`` of the snapshot held - its slot, whether that slot had been stepped, the device memory of the
+        store - or ``None`` when there is none (never taken, dropped, or void)."""
+        st, sp, by = C.c_int32(), C.c_int32(), C.c_int64()
+        if self._lib.vds_snapshot_info(self._h, C.byref(st), C.byref(sp), C.byref(by)):
+            return None
+        return dict(step=st.value, stepped=bool(sp.value), bytes=by.value)
+
+    def drop_snapshot(self):
+        """Free the snapshot's storage (``vds_snapshot_drop``)."""
+        self._chk(self._lib.vds_snapshot_drop(self._h))
+
     def run(self, n_ticks: int):
         self._chk(self._lib.vds_run(self._h, int(n_ticks)))
 
