@@ -1,0 +1,958 @@
+"""Model-based test of the host API: seeded random scripts of API calls on ONE ``BatchedDispatchEnv`` handle, checked call by call
+against a model built from CPU oracles (``Script``; ``run_script`` drives one to its end, or replays a prefix).
+
+What the kernels compute is covered elsewhere; this drives the host state that decides WHICH kernel runs on WHICH tables - the day
+graphs of ``run`` / ``run_hooked`` and their keys, the table generations, the reset image, the snapshot and its validity, the reload
+paths, the dispatch sequence numbers, the sticky error bits - through orders of calls that no fixed-sequence test composes.
+
+The oracle cannot be cloned, so a replica is a LINEAGE (start nodes, order day, the dispatches of every slot) and the oracle of a
+restored replica is a fresh one replayed on the lineage of its source.  The script is drawn from the MODEL alone (list positions
+come from the model's lists), never from what the engine answers: the same seed gives the same calls on every engine, which is
+what lets ``tests/test_api_script_model.py`` prove the harness on a stand-in engine without a GPU.
+
+Snapshot validity follows include/vds.h: VOID after ``load_orders*`` / ``set_replica_days`` / the first supply-in-place request (which
+is made before the first reset here, when there is no snapshot yet) / ``drop_snapshot``; UNKNOWN after what cannot be seen from
+outside - a ``reset`` / ``reset_random`` that may regrow automatic idle tables, ``set_idle_cap`` (which may or may not replace them), any
+reset of a handle whose dense base form is still open to ``adapt_dense``; VALID otherwise.  In state UNKNOWN a restore may answer
+"no snapshot" (then there is none) or restore what the model expects.
+
+Calls that the header makes illegal are never drawn: after a load, ``set_replica_days`` or ``set_idle_cap`` only a reset, another
+load / map / cap / ``set_run_groups`` or a restore that must be refused (state VOID) may follow, until a reset has been issued -
+``reset_again`` only after ``set_idle_cap`` (the start nodes may not survive a load or another map).  A restore right behind
+``set_idle_cap`` is drawn in state UNKNOWN too: a cap that replaced no table keeps the snapshot, so either "no snapshot" or the
+snapshot's state is the answer; the reset that the header asks for follows all the same."""
+import os
+import random
+import re
+from types import SimpleNamespace
+
+import numpy as np
+
+from oracle.oracle import Oracle
+from outcome_expect import processed_planes
+from test_gpu_fuzz import random_case
+from test_gpu_parity import check_lists
+from vehicles_dispatch_simulator_amd.env import neighbors_to_csr
+
+VALID, VOID, UNKNOWN = "VALID", "VOID", "UNKNOWN"
+COUNTERS = ("order_num", "reject_num", "matched", "wait_sum", "dispatch_num", "dispatch_cost", "sum_order_value", "evals")
+PLANES = ("idle_pre", "idle_now", "supply", "cl_orders", "inflight")
+NO_SNAPSHOT = "libvds error -4: .*no snapshot"
+DISPATCH_ERROR = "libvds error -4: dispatch of an idle position"
+READS = ("obs", "obs_torch", "obs_inplace", "counters", "total_counters", "orders", "lists", "vehicles", "idle_heads", "outcomes")
+KINDS = ("step", "dispatch_host", "dispatch_ex", "dispatch_dev", "advance", "run", "run_hooked", "reset", "reset_again", "reset_random",
+         "snapshot", "restore", "restore_torch", "drop_snapshot", "load_orders", "load_order_days", "set_replica_days", "set_run_groups",
+         "set_idle_cap") + READS
+# the state-moving classes whose ordered pairs the corpus has to contain (tests/test_api_script_model.py)
+MOVERS = ("step-loop", "run", "run_hooked", "reset", "reset_again", "reset_random", "snapshot", "restore", "load_orders", "load_order_days",
+          "set_replica_days", "set_run_groups", "set_idle_cap")
+MOVER_OF = dict({k: k for k in MOVERS}, step="step-loop", dispatch_host="step-loop", dispatch_ex="step-loop", dispatch_dev="step-loop",
+                advance="step-loop", restore_torch="restore")
+NEEDS_RESET = ("load_orders", "load_order_days", "set_replica_days", "set_idle_cap")
+
+
+def legal_pair(a, b):
+    """May a call of class ``b`` be the next state-moving call after one of class ``a``?  (module docstring, last paragraph.)"""
+    if a in NEEDS_RESET:
+        if b in ("step-loop", "run", "run_hooked", "snapshot"):
+            return False
+        if b == "reset_again":
+            return a == "set_idle_cap"
+    return True
+
+
+def case(seed):
+    """A city and a configuration drawn like ``test_gpu_fuzz.random_case`` (same axes), 2-4 order days, R, idle_cap, switches."""
+    c = SimpleNamespace(seed=seed)
+    cost, n2c, nbr, V, rel, pick, dele, valid, cfg = random_case(30_000 + seed)
+    rng = np.random.default_rng(31_000 + seed)
+    c.cost, c.n2c, c.V, c.valid, c.cfg = cost, n2c, V, valid, cfg
+    c.N, c.C = cost.shape[0], len(nbr)
+    c.off, c.idx = neighbors_to_csr(nbr)
+    days = [(rel, pick, dele)]
+    for d in range(int(rng.integers(1, 4))):        # (test_gpu_fuzz.days_case: different length and density, so different tick grids)
+        O = int(rng.integers(2, 1200))
+        span = int(rng.integers(20, 1440))
+        r2 = (np.sort(rng.integers(0, span, size=O)) + int(rng.integers(0, 50))).astype(np.int32)
+        days.append((r2, rng.choice(valid, size=O).astype(np.int32), rng.choice(valid, size=O).astype(np.int32)))
+    c.days = days
+    c.R = int(rng.integers(1, 9)) if rng.random() < 0.72 else int(rng.choice([17, 40, 70]))
+    c.idle_cap = max(64, V) if rng.random() < 0.5 else 0          # explicit / left to the reset
+    fg = cfg["force_generic"]
+    lr = np.random.default_rng(90_000 + seed)
+    c.dense_debug, c.environ = None, {}
+    if fg == 0 and lr.random() < 0.75:              # (else: the library's own choice, which adapt_dense may change between episodes)
+        c.dense_debug = (int(lr.choice([16, 8])), int(lr.choice([0, 0, 8, 24, 40])), int(lr.choice([0, 0, 2, 5])), int(lr.random() < 0.1) | (2 if lr.random() < 0.3 else 0))
+    if fg == 0 and cfg["neighbor"] and lr.random() < 0.34:
+        c.environ["VDS_DENSE_DFS"] = "0"
+    if fg == 0 and lr.random() < 0.34:
+        c.environ["VDS_DENSE_TICK_FORMS"] = "alt"
+    c.adaptable = fg == 0 and c.dense_debug is None and "VDS_DENSE_TICK_FORMS" not in c.environ
+    c.want_sup = fg == 0 and not cfg["neighbor"] and rng.random() < 0.4
+    c.n_days0 = int(rng.integers(1, min(len(days), c.R) + 1))    # days resident after the first load
+    return c
+
+
+class switches:
+    """The per-case environment switches, set around every load of the case (the library reads them when tables are made)."""
+
+    def __init__(self, c):
+        self.env = c.environ
+
+    def __enter__(self):
+        self.saved = {k: os.environ.get(k) for k in self.env}
+        os.environ.update(self.env)
+
+    def __exit__(self, *a):
+        for k, v in self.saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def make_oracle(c, day):
+    return Oracle(c.cost, c.n2c, c.off, c.idx, c.cfg["depth"], c.cfg["neighbor"], day[0], day[1], day[2], c.V,
+                  tick_minutes=c.cfg["tick"], reject_threshold=c.cfg["threshold"])
+
+
+def py_random_nodes(c, seed):
+    """InitVehiclesIntoCluster with ``random.Random(seed)`` (simulator.py:249-258), as tests/test_gpu_edge_cases.py models it."""
+    rng = random.Random(int(seed))
+    out = np.empty(c.V, dtype=np.int32)
+    for v in range(c.V):
+        while True:
+            node = rng.choice(range(c.N))
+            if c.n2c[node] >= 0:
+                break
+        out[v] = node
+    return out
+
+
+class Lineage:
+    """One replica: start nodes, order day, the dispatches of every slot, and the oracle that stands where the replica stands."""
+
+    def __init__(self, c, init, day, hist=None):
+        self.c, self.init, self.day = c, np.array(init, dtype=np.int32), day
+        self.o = make_oracle(c, day)
+        self.o.reset(self.init)
+        self.pick_cl = c.n2c[np.asarray(day[1], dtype=np.int64)]
+        self.t, self.stepped, self.acts = 0, False, {}
+        self.outc = np.zeros((c.C, 4), dtype=np.int64)          # order outcomes of the slot stepped last
+        if hist is not None:
+            t, stepped, acts = hist
+            for s in range(t):
+                self.step(track=s == t - 1 and not stepped)
+                for a in acts.get(s, ()):
+                    self.dispatch(*a)
+                self.advance()
+            if stepped:
+                self.step()
+                for a in acts.get(t, ()):
+                    self.dispatch(*a)
+
+    @property
+    def live(self):
+        return self.t < self.o.num_ticks
+
+    def step(self, track=True):
+        if self.live:
+            before = self.o.orders()["status"] if track else None
+            self.o.begin_tick()
+            if track:
+                res = self.o.orders()
+                self.outc = processed_planes(before, res["status"], self.pick_cl, res["wait"], res["value"], self.c.C)
+        elif track:
+            self.outc = np.zeros((self.c.C, 4), dtype=np.int64)
+        self.stepped = True
+
+    def dispatch(self, veh, tgt, arr=None, counted=True):
+        if arr is None and counted:
+            self.o.dispatch(veh, tgt)
+        else:
+            self.o.dispatch_at(veh, tgt, arrive_min=arr, counted=counted)
+        self.acts.setdefault(self.t, []).append((np.array(veh), np.array(tgt), None if arr is None else np.array(arr), counted))
+
+    def advance(self):
+        if self.live:
+            self.o.end_tick()
+        self.t += 1
+        self.stepped = False
+
+    def run(self, n):
+        for k in range(n):
+            self.step(track=k == n - 1)
+            self.advance()
+
+    def history(self):
+        return self.t, self.stepped, {k: list(v) for k, v in self.acts.items()}
+
+    def idle(self):
+        """(idle_off, idle_veh) of the oracle's lists."""
+        L = self.o.lists()
+        return L["idle_off"], L["idle_veh"]
+
+
+def to_device(env, a):
+    if hasattr(env, "to_device"):           # (the stand-in engine of tests/test_api_script_model.py)
+        return env.to_device(a)
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def to_host(x):
+    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
+
+
+def new_stats():
+    return dict(kinds={}, pairs={}, restores=0, restores_unknown=0, restores_void=0, restores_valid=0, restores_valid_ok=0,
+                restore_after_dispatch=0, hook_applied=0, hook_refused=0, run_same=0, run_moved=0, run_after_change=0, run_eager=0, refused_length=0, refused_twice=0,
+                restore_none_ok=0, refused_map_range=0, refused_map_day=0, calls=[], kernels=set(), storage=set(), layouts=set())
+
+
+def show(v):
+    if isinstance(v, np.ndarray):
+        v = v.tolist()
+    s = repr(v)
+    return s if len(s) <= 160 else s[:150] + "...<%d chars>" % len(s)
+
+
+class ScriptFailure(AssertionError):
+    pass
+
+
+class Script:
+    """One handle, its model and the generator of its calls.  ``next()`` draws, issues and checks one call; False when the script is
+    over (the open day has then been finished and compared in full)."""
+
+    def __init__(self, env_factory, seed, stream=None, stats=None):
+        self.c = c = case(seed)
+        self.seed, self.factory, self.stream = seed, env_factory, stream
+        self.rng = np.random.default_rng(40_000 + seed)
+        self.stats = new_stats() if stats is None else stats
+        self.log, self.n_calls, self.done = [], 0, False
+        self.length = int(self.rng.integers(40, 47))
+        self.n0 = 8 + int(self.rng.integers(0, 24))
+        # the model
+        self.lines, self.init = None, None
+        self.days, self.rd = [], None                   # resident days (indices into c.days) and the replica -> resident day map
+        self.t, self.stepped, self.T = 0, False, 0
+        self.snap, self.snap_state = None, VOID
+        self.need_reset = 2                             # 0 no; 1 a reset* must follow, reset_again will do; 2 reset / reset_random
+        self.expect_err = False
+        self.dispatched_in_slot = False
+        self.prev_mover, self.sup = None, None
+        self.hook_cache, self.graph_key, self.tables = None, None, 0      # (tables: counts what re-makes or re-keys the tables)
+        pairs = [(a, b) for a in MOVERS for b in MOVERS if legal_pair(a, b)]
+        idx = seed % 1000 + (32 if seed >= 1000 else 0)        # (the corpus' scripts 0 .. 47: their wishes go round the pairs evenly)
+        self.wishes = [pairs[(idx + 48 * j) % len(pairs)] for j in range(14)]
+        self.pending = []
+        self.held, self.held_src = None, None           # the action tensor of the last hooked run on the device, and what it was made from
+        self.env = None
+        self.open()
+
+    # ---- the handle -----------------------------------------------------------------------------------------------------------
+    def open(self):
+        c = self.c
+        kw = dict(replicas=c.R, vehicles=c.V, depth_limit=c.cfg["depth"], neighbor_can_server=c.cfg["neighbor"], tick_minutes=c.cfg["tick"],
+                  reject_threshold=c.cfg["threshold"], ring_ticks=c.cfg["ring_ticks"], force_generic=c.cfg["force_generic"], idle_cap=c.idle_cap,
+                  ring_cap=max(16, c.V), far_cap=max(64, c.V))
+        if c.dense_debug is not None:
+            kw["dense_debug"] = c.dense_debug
+        if self.stream is not None:
+            kw["stream"] = self.stream
+        with switches(c):
+            self.env = self.factory(c.cost, c.n2c, c.off, c.idx, **kw)
+        ids = list(range(c.n_days0)) if not self.days else list(self.days)
+        rd = self.block_map(len(ids)) if self.rd is None else self.rd
+        init = self.fresh_init() if self.init is None else self.init
+        self.snap, self.snap_state, self.need_reset, self.lines = None, VOID, 2, None
+        self.pending = [("load_orders", dict(day=ids[0])) if len(ids) == 1 else ("load_order_days", dict(days=ids, rd=rd)), ("reset", dict(init=init))]
+
+    def reopen(self):
+        """Close the handle and open a fresh one on the same city; the resident days and the start nodes are loaded again."""
+        self.env.close()
+        self.log.append("    -- handle closed and opened again")
+        self.open()
+
+    def close(self):
+        if self.env is not None:
+            self.env.close()
+            self.env = None
+
+    # ---- draws ----------------------------------------------------------------------------------------------------------------
+    def block_map(self, n):
+        return (np.arange(self.c.R) * n // self.c.R).astype(np.int32)
+
+    def fresh_init(self):
+        c = self.c
+        return self.rng.choice(c.valid, size=(c.R, c.V)).astype(np.int32) if c.V else np.zeros((c.R, 0), np.int32)
+
+    def draw_init(self):
+        c, how = self.c, int(self.rng.integers(0, 3))
+        if how == 0 and self.init is not None and c.V:                      # the start nodes of before, permuted
+            return np.stack([self.rng.permutation(row) for row in self.init]).astype(np.int32)
+        init = self.fresh_init()
+        if how == 1 and c.V:                                                # crowded: most vehicles of a replica in ONE cluster
+            cl = c.n2c[c.valid]
+            big = np.flatnonzero(c.n2c == np.bincount(cl).argmax())
+            for r in range(c.R):
+                move = self.rng.random(c.V) < 0.8
+                init[r, move] = self.rng.choice(big, size=int(move.sum()))
+        return init
+
+    def draw_map(self, n):
+        """A replica -> day map onto all n days (R >= n): aligned blocks, interleaved, or one day per row at random."""
+        R, how = self.c.R, int(self.rng.integers(0, 3))
+        if how == 0:
+            return self.block_map(n)
+        if how == 1:
+            return (np.arange(R) % n).astype(np.int32)
+        rd = self.rng.integers(0, n, size=R).astype(np.int32)
+        rd[self.rng.permutation(R)[:n]] = np.arange(n)
+        return rd
+
+    def draw_days(self):
+        c = self.c
+        n = int(self.rng.integers(1, min(len(c.days), c.R) + 1))
+        ids = [int(x) for x in self.rng.permutation(len(c.days))[:n]]
+        return ids, self.draw_map(n)
+
+    def live(self):
+        return [r for r, ln in enumerate(self.lines) if ln.live]
+
+    def draw_moves(self, kmax):
+        """{replica: (flat positions in slot order, vehicles, targets, (cluster, position) pairs)} for some live replicas."""
+        mv = {}
+        for r in self.live():
+            if self.rng.random() < 0.25:
+                continue
+            off, veh = self.lines[r].idle()
+            n = int(off[-1])
+            if n == 0:
+                continue
+            flat = self.rng.choice(n, size=min(n, int(self.rng.integers(1, kmax + 1))), replace=False)
+            cl = np.searchsorted(off, flat, side="right") - 1
+            mv[r] = (flat, veh[flat].copy(), self.rng.choice(self.c.valid, size=flat.size).astype(np.int32), [(int(a), int(f - off[a])) for a, f in zip(cl, flat)])
+        return mv
+
+    def same_day_map(self, how):
+        R, rd = self.c.R, np.asarray(self.snap["rd"])
+        src = np.arange(R)
+        for d in np.unique(rd):
+            rows = np.flatnonzero(rd == d)
+            if how == "perm":
+                src[rows] = self.rng.permutation(rows)
+            elif how == "one":
+                src[rows] = rows[int(self.rng.integers(0, rows.size))]
+            elif how == "random":
+                src[rows] = self.rng.choice(rows, size=rows.size)
+        return src.astype(np.int32)
+
+    def weights(self):
+        w = {}
+        vd = self.snap_state
+        if self.need_reset:
+            w.update(reset=9, reset_random=3, load_orders=.3, load_order_days=.4, set_run_groups=.4, set_idle_cap=.3)
+            if self.need_reset == 1:
+                w["reset_again"] = 8
+            w["set_replica_days"] = .4 if len(self.days) > 1 else .2
+            if self.prev_mover == "set_idle_cap" and self.need_reset == 1:
+                w["restore"] = .6                  # (a cap that replaced no table keeps the snapshot: the header leaves the answer open)
+            elif vd == VOID:
+                w["restore"] = .2
+            return w
+        for k in READS:
+            w[k] = .3
+        w.update(reset=.5, reset_again=.8, reset_random=.4, snapshot=1.3, load_orders=.2, load_order_days=.3, set_run_groups=.4, set_idle_cap=.3)
+        w["restore"] = {VALID: 2.6, UNKNOWN: .4, VOID: .05}[vd]
+        if len(self.days) == 1:
+            w["restore_torch"] = {VALID: .9, UNKNOWN: .1, VOID: .03}[vd]
+        w["set_replica_days"] = .3 if len(self.days) > 1 else .15
+        if self.snap is not None:
+            w["drop_snapshot"] = .9
+        if self.stepped:
+            w["advance"] = 4
+            if any(int(self.lines[r].idle()[0][-1]) > 0 for r in self.live()):
+                w.update(dispatch_host=2, dispatch_ex=2, dispatch_dev=2.5)
+        elif self.t < self.T:
+            w.update(step=5, run=1.6, run_hooked=1.3)
+        return w
+
+    def draw_kind(self):
+        w = self.weights()
+        by_class = {}
+        for k in w:
+            if k in MOVER_OF:
+                by_class.setdefault(MOVER_OF[k], []).append(k)
+        if self.stepped and not self.need_reset and self.rng.random() < 0.5:      # an open slot is worked on before anything is steered
+            ks = [k for k in ("advance", "dispatch_host", "dispatch_ex", "dispatch_dev") if k in w]
+            p = np.array([w[k] for k in ks], dtype=np.float64)
+            return ks[int(self.rng.choice(len(ks), p=p / p.sum()))]
+        u = self.rng.random()
+        follow = [b for a, b in self.wishes if a == self.prev_mover and b in by_class]
+        lead = [a for a, b in self.wishes if a in by_class and a != self.prev_mover]
+        pick = None
+        if follow and u < 0.9:
+            pick = follow[0]
+        elif lead and u >= 0.9:
+            pick = lead[0]
+        if pick == "restore" and follow and self.snap_state == VOID and not self.need_reset and self.rng.random() < 0.5:
+            pick = None
+        if pick == "restore" and not follow and self.snap_state == VOID and not self.need_reset:
+            pick = "snapshot"                   # (led to with a snapshot at hand: the refusal of state VOID is drawn often enough)
+        if pick is not None:
+            ks = by_class[pick]
+            if pick == "step-loop":             # (the class is entered by whatever the slot allows next)
+                ks = [k for k in ks if k in ("step", "advance")] or ks
+            return ks[int(self.rng.integers(0, len(ks)))]
+        ks = sorted(w)
+        p = np.array([w[k] for k in ks], dtype=np.float64)
+        return ks[int(self.rng.choice(len(ks), p=p / p.sum()))]
+
+    def draw(self):
+        """The next call as (kind, arguments): legal as the model stands, or marked with the refusal it must meet."""
+        if self.pending:
+            return self.pending.pop(0)
+        c, rng, kind = self.c, self.rng, self.draw_kind()
+        a = {}
+        if kind == "reset":
+            a["init"] = self.draw_init()
+        elif kind == "reset_random":
+            a["seeds"] = rng.integers(0, 2**40, size=c.R).astype(np.uint64)
+        elif kind == "load_orders":
+            a["day"] = int(rng.integers(0, len(c.days)))
+        elif kind == "load_order_days":
+            a["days"], a["rd"] = self.draw_days()
+            if rng.random() < 0.25:
+                a["default_map"] = True
+                a["rd"] = self.block_map(len(a["days"]))
+        elif kind == "set_replica_days":
+            a["rd"] = self.draw_map(len(self.days))
+        elif kind == "set_run_groups":
+            a["groups"] = int(rng.integers(0, 5))
+        elif kind == "set_idle_cap":
+            a["cap"] = max(c.V, 1) + int(rng.choice([0, 1, 64, 200]))      # (never below V: no list can overflow)
+            wished = any(x == "set_idle_cap" and y != "reset_again" for x, y in self.wishes)
+            self.pending = [("reset_again", {})] if self.need_reset < 2 and not wished and rng.random() < 0.7 else []
+        elif kind == "run":
+            left = self.T - self.t
+            u = rng.random()
+            gk = self.graph_key
+            if rng.random() < 0.3:
+                n = int(rng.integers(1, 8))   # eager: no day graph
+            elif gk is not None and gk[1] <= left and u < 0.8:
+                n = gk[1]                   # the count of the day graph of before: a replay at the same first slot, else an update in place
+            elif self.t == 0 and u < 0.8:
+                n = self.n0                 # (the script's own count from slot 0: it comes back after every reset)
+            elif u < 0.9:
+                n = int(rng.integers(8, 40))
+            else:
+                n = left
+            a["n"] = max(1, min(n, left))
+            u = rng.random()
+            if self.t == 0 and a["n"] >= 8 and u < 0.3:                     # the same day graph again from the same slot: a replay
+                self.pending = [("reset_again", {}), ("run", dict(n=a["n"]))]
+            elif a["n"] >= 8 and 2 * a["n"] <= left and u < 0.5:            # ... and from the slot behind it: an update in place
+                self.pending = [("run", dict(n=a["n"]))]
+        elif kind == "run_hooked":
+            left = self.T - self.t
+            hc = self.hook_cache
+            if hc is not None and rng.random() < 0.4 and hc["n"] <= left:   # the hooked call of before again (same tensor: same key)
+                a.update(hc)
+            else:
+                a["n"] = max(1, min(left, int(rng.choice([1, 3, 8, 12, 30, left]))))
+                a["planes"] = int(rng.integers(0, 32))
+                a["outcomes"] = bool(rng.random() < 0.5)
+                a["L"] = int(rng.choice([0, 1, 4, 64]))
+                a["acts"] = None
+                if rng.random() < 0.65 and c.V:
+                    K = int(rng.integers(1, min(c.C, 3) + 1))
+                    acts = np.full((c.R, K, 3), -1, dtype=np.int32)
+                    for r in range(c.R):
+                        cls = rng.permutation(c.C)[:K]
+                        for k in range(K):
+                            if rng.random() < 0.8:
+                                acts[r, k] = (cls[k], 0, rng.choice(c.valid))
+                    a["acts"] = acts
+                self.hook_cache = dict(a)
+        elif kind in ("dispatch_host", "dispatch_ex"):
+            mv = self.draw_moves(4)
+            a["moves"] = {r: (m[1], m[2], m[3]) for r, m in mv.items()}
+            if kind == "dispatch_ex":
+                a["extra"] = {}
+                for r, m in mv.items():
+                    o = self.lines[r].o
+                    loc = o.vehicles()["loc"][m[1]]
+                    arr = (o.now_min + c.cost[m[2], loc] + rng.integers(0, 25, size=m[1].size)).astype(np.int32)
+                    a["extra"][r] = (arr, bool(rng.random() < 0.5))
+        elif kind == "dispatch_dev":
+            mv = self.draw_moves(6)
+            per = {r: [(cl, pos, int(t)) for (cl, pos), t in zip(m[3], m[2])] for r, m in mv.items()}
+            a["moves"] = {r: (m[1], m[2], m[3]) for r, m in mv.items()}
+            a["refused"] = None
+            if per and rng.random() < 0.4:          # one action the engine must refuse, behind the replica's good ones
+                r = sorted(per)[int(rng.integers(0, len(per)))]
+                off, _ = self.lines[r].idle()
+                if rng.random() < 0.5:
+                    cl = int(rng.integers(0, c.C))
+                    per[r].append((cl, int(off[cl + 1] - off[cl]), int(rng.choice(c.valid))))       # position == list length
+                    a["refused"] = (r, "length")
+                else:
+                    first = per[r][int(rng.integers(0, len(per[r])))]
+                    per[r].append((first[0], first[1], int(rng.choice(c.valid))))                   # a position named twice: the first stands
+                    a["refused"] = (r, "twice")
+            K = max([len(v) for v in per.values()] + [1])
+            K = min(64, K + int(rng.choice([0, 1, 3, 64])))
+            acts = np.full((c.R, K, 3), -1, dtype=np.int32)
+            for r, lst in per.items():
+                slots = np.sort(rng.choice(K, size=len(lst), replace=False))                        # empty slots in between
+                for s, act in zip(slots, lst):
+                    acts[r, s] = act
+            a["acts"] = acts
+        elif kind in ("restore", "restore_torch"):
+            vd = self.snap_state
+            a["src"], a["expect"] = None, None
+            if vd == VOID or self.snap is None:
+                a["expect"] = NO_SNAPSHOT
+                a["src"] = np.arange(c.R, dtype=np.int32) if kind == "restore_torch" else None
+            else:
+                rd = np.asarray(self.snap["rd"])
+                how = str(rng.choice(["none", "identity", "perm", "one", "random", "bad"], p=[.5, .04, .09, .08, .07, .22]))
+                if vd == VALID and np.unique(rd).size > 1 and rng.random() < 0.45:
+                    how = "bad"
+                if kind == "restore_torch" and how in ("none", "bad"):
+                    how = "perm"
+                if how == "bad" and vd != VALID:
+                    how = "random"
+                if how == "identity":
+                    a["src"] = np.arange(c.R, dtype=np.int32)
+                elif how in ("perm", "one", "random"):
+                    a["src"] = self.same_day_map(how)
+                elif how == "bad":
+                    src = np.arange(c.R, dtype=np.int32)
+                    r = int(rng.integers(0, c.R))
+                    other = np.flatnonzero(rd != rd[r])
+                    if other.size and rng.random() < 0.65:
+                        src[r] = other[0]
+                        a["expect"] = "libvds error -1: .*order days per replica"
+                    else:
+                        src[r] = c.R if rng.random() < 0.5 else -1
+                        a["expect"] = "libvds error -1: "
+                    a["src"] = src
+        elif kind == "obs_torch":
+            a["planes"] = int(rng.integers(1, 32))
+        elif kind in ("lists", "vehicles"):
+            a["r"] = int(rng.integers(0, c.R))
+        elif kind == "idle_heads":
+            a["L"] = int(rng.choice([1, 4, 64]))
+        return kind, a
+
+    # ---- one call -------------------------------------------------------------------------------------------------------------
+    def next(self, upto=None):
+        if self.done or (upto is not None and self.n_calls >= upto):
+            return False
+        try:
+            if self.n_calls >= self.length and not self.pending and not self.need_reset:       # the open day is finished
+                if self.stepped:
+                    kind, a = "advance", {}
+                elif self.t < self.T:
+                    kind, a = "run", dict(n=self.T - self.t)
+                else:
+                    self.finish()
+                    return False
+            else:
+                kind, a = self.draw()
+            self.log.append("%3d %s(%s)" % (self.n_calls, kind, ", ".join("%s=%s" % (k, show(v)) for k, v in a.items())))
+            self.issue(kind, a)
+            self.n_calls += 1
+        except ScriptFailure:
+            raise
+        except BaseException as e:
+            if isinstance(e, KeyboardInterrupt):
+                raise
+            raise ScriptFailure("API script of seed %d failed at call %d: %s: %s\nthe script so far (replay: run_script(env_factory, %d, upto=%d)):\n%s"
+                                % (self.seed, self.n_calls, type(e).__name__, e, self.seed, self.n_calls + 1, "\n".join(self.log))) from e
+        return True
+
+    def count(self, kind):
+        st = self.stats
+        st["kinds"][kind] = st["kinds"].get(kind, 0) + 1
+        m = MOVER_OF.get(kind)
+        if m is not None:
+            if self.prev_mover is not None and not (m == "step-loop" and self.prev_mover == "step-loop" and kind != "step"):
+                st["pairs"][(self.prev_mover, m)] = st["pairs"].get((self.prev_mover, m), 0) + 1
+                if (self.prev_mover, m) in self.wishes:
+                    self.wishes.remove((self.prev_mover, m))
+            self.prev_mover = m
+
+    def refused(self, pattern, fn):
+        try:
+            fn()
+        except Exception as e:
+            assert re.search(pattern, str(e)), "expected a refusal matching %r, got: %s" % (pattern, e)
+            return
+        raise AssertionError("expected a refusal matching %r, the call succeeded" % pattern)
+
+    def issue(self, kind, a):
+        env, c = self.env, self.c
+        self.count(kind)
+        full = False
+        if kind == "step":
+            env.step()
+            for ln in self.lines:
+                ln.step()
+            self.stepped, self.dispatched_in_slot = True, False
+        elif kind == "advance":
+            env.advance()
+            for ln in self.lines:
+                ln.advance()
+            self.t, self.stepped = self.t + 1, False
+        elif kind in ("dispatch_host", "dispatch_ex"):
+            rep, cl, pos, tgt, arr, cnt = [], [], [], [], [], []
+            for r, (veh, tg, cp) in a["moves"].items():
+                for i, (cc, pp) in enumerate(cp):
+                    rep.append(r); cl.append(cc); pos.append(pp); tgt.append(int(tg[i]))
+                    if kind == "dispatch_ex":
+                        arr.append(int(a["extra"][r][0][i])); cnt.append(int(a["extra"][r][1]))
+            if rep:
+                if kind == "dispatch_ex":
+                    env.apply_dispatch(rep, cl, pos, tgt, arrive_min=arr, counted=cnt)
+                else:
+                    env.apply_dispatch(rep, cl, pos, tgt)
+                self.dispatched_in_slot = True
+            for r, (veh, tg, cp) in a["moves"].items():
+                if kind == "dispatch_ex":
+                    self.lines[r].dispatch(veh, tg, a["extra"][r][0], a["extra"][r][1])
+                else:
+                    self.lines[r].dispatch(veh, tg)
+        elif kind == "dispatch_dev":
+            held = to_device(env, a["acts"])
+            env.apply_dispatch_torch(held)
+            for r, (veh, tg, cp) in a["moves"].items():
+                self.lines[r].dispatch(veh, tg)
+                self.dispatched_in_slot = True
+            self.expect_err = a["refused"] is not None
+            if a["refused"] is not None:
+                self.stats["refused_" + a["refused"][1]] += 1
+            self.settle()
+            del held
+        elif kind == "run":
+            self.stats["run_eager"] += a["n"] < 8
+            if a["n"] >= 8:                     # (the day graph: replayed for the same first slot and count, else rebuilt or updated in place)
+                st, key = self.stats, (self.t, a["n"], self.tables)
+                if self.graph_key is not None and key[1] == self.graph_key[1]:
+                    st["run_same" if key == self.graph_key else "run_after_change" if key[2] != self.graph_key[2] else "run_moved"] += 1
+                self.graph_key = key
+            env.run(a["n"])
+            for ln in self.lines:
+                ln.run(a["n"])
+            self.t += a["n"]
+        elif kind == "run_hooked":
+            self.run_hooked(a)
+        elif kind in ("reset", "reset_again", "reset_random"):
+            if kind == "reset":
+                env.reset(a["init"])
+                self.init = a["init"]
+            elif kind == "reset_random":
+                env.reset_random(a["seeds"])
+                self.init = np.stack([py_random_nodes(c, s) for s in a["seeds"]]) if c.R else self.init
+            else:
+                env.reset_again()
+            self.lines = [Lineage(c, self.init[r], c.days[self.days[self.rd[r]]]) for r in range(c.R)]
+            self.t, self.stepped, self.need_reset, self.expect_err = 0, False, 0, False
+            self.T = max(ln.o.num_ticks for ln in self.lines)
+            assert env.T == self.T, "T: engine %d, model %d" % (env.T, self.T)
+            if self.snap is not None and (c.adaptable or (kind != "reset_again" and c.idle_cap == 0)):
+                self.snap_state = UNKNOWN
+            full = True
+        elif kind == "snapshot":
+            env.snapshot()
+            self.snap = dict(rows=[(ln.init, ln.day, ln.history()) for ln in self.lines], rd=np.array(self.rd), t=self.t, stepped=self.stepped)
+            self.snap_state = VALID
+            info = env.snapshot_info()
+            assert info is not None and info["step"] == self.t and info["stepped"] == self.stepped and info["bytes"] > 0, info
+        elif kind == "drop_snapshot":
+            env.drop_snapshot()
+            self.snap, self.snap_state = None, VOID
+            assert env.snapshot_info() is None
+        elif kind in ("restore", "restore_torch"):
+            full = self.restore(kind, a)
+        elif kind in ("load_orders", "load_order_days", "set_replica_days"):
+            with switches(c):
+                if kind == "load_orders":
+                    env.load_orders(*c.days[a["day"]])
+                    self.days, self.rd = [a["day"]], np.zeros(c.R, dtype=np.int32)
+                elif kind == "load_order_days":
+                    env.load_order_days([c.days[d] for d in a["days"]], None if a.get("default_map") else a["rd"])
+                    self.days, self.rd = list(a["days"]), np.array(a["rd"])
+                else:
+                    env.set_replica_days(a["rd"])
+                    self.rd = np.array(a["rd"])
+                if c.want_sup and kind != "set_replica_days":      # SupplyExpect in place, asked for before the reset (the first request voids a snapshot: there is none now)
+                    self.sup = None
+                    try:
+                        self.sup = env.supply_inplace_torch()
+                    except Exception as e:
+                        assert "dense layout only" in str(e) or "order days per replica" in str(e), e
+            self.snap, self.snap_state, self.need_reset, self.lines = None, VOID, 2, None
+            self.tables += 1
+            assert env.snapshot_info() is None
+            st = self.stats
+            st["kernels"].add(env.main_kernel())
+            lay = env.layout()
+            st["layouts"].add((env.main_kernel(), lay["dense"], lay["dense_st"]))
+            if len(set(self.rd.tolist())) > 1:      # how the replicas of a mixed map are stored, seen from outside: the in-place planes
+                try:                                # are refused for regrouped storage and stand for one order stream per row
+                    env.obs_inplace_torch()
+                    mixed = any(len(set(self.rd[i:i + 16].tolist())) > 1 for i in range(0, c.R, 16))
+                    st["storage"].add("stream per row" if mixed else "aligned groups")
+                except Exception as e:
+                    assert "regrouped by order day" in str(e), e
+                    st["storage"].add("regrouped")
+        elif kind == "set_run_groups":
+            env.set_run_groups(a["groups"])
+            self.tables += 1
+        elif kind == "set_idle_cap":
+            env.set_idle_cap(a["cap"])
+            self.tables += 1
+            assert env.idle_cap >= min(a["cap"], max(c.V, 1)), env.idle_cap
+            if self.snap is not None:
+                self.snap_state = UNKNOWN
+            self.need_reset = max(self.need_reset, 1)
+            self.lines = None if self.need_reset == 2 else self.lines
+        else:
+            self.read(kind, a)
+            return
+        if self.need_reset and kind in ("restore", "restore_torch") and self.lines is not None and self.snap_state == VALID and a["expect"] is None:
+            self.settle()           # restored right behind a set_idle_cap that replaced no table: the state is the snapshot's; a reset
+            self.check(True)        # must follow all the same
+            self.lines = None if self.need_reset == 2 else self.lines
+            return
+        if self.lines is None or self.need_reset:
+            return
+        self.settle()
+        self.check(full or self.n_calls % 8 == 7)
+
+    def settle(self):
+        """The dispatch error that the next ``sync`` must report, exactly when the model expects one; once."""
+        err = None
+        try:
+            self.env.sync()
+        except Exception as e:
+            err = str(e)
+        if self.expect_err:
+            assert err is not None and re.search(DISPATCH_ERROR, err), "expected the dispatch error at sync, got %r" % err
+            self.env.sync()         # (reported once)
+        else:
+            assert err is None, "sync: %s" % err
+        self.expect_err = False
+
+    def run_hooked(self, a):
+        env, c, n = self.env, self.c, a["n"]
+        pl = a["planes"]
+        kw = dict(idle_pre=bool(pl & 1), idle_now=bool(pl & 2), supply=bool(pl & 4), cl_orders=bool(pl & 8), inflight=bool(pl & 16))
+        blk = env.obs_torch()                       # the blocks the day writes alias library memory at fixed addresses
+        outc = env.outcomes_torch() if a["outcomes"] else None
+        heads = env.idle_heads_torch(a["L"]) if a["L"] else None
+        if a["acts"] is not None and self.held_src is not a["acts"]:       # (the tensor of before again: the same address, the graph's key)
+            self.held, self.held_src = to_device(env, a["acts"]), a["acts"]
+        env.run_hooked(n, actions=self.held if a["acts"] is not None else None, outcomes=a["outcomes"], idle_heads=a["L"], **kw)
+        seen = []
+        for r, ln in enumerate(self.lines):
+            for k in range(n):
+                ln.step(track=k == n - 1)
+                last = None
+                if k == n - 1:          # what the slot's planes show: behind the step, before the slot's actions
+                    off, veh = ln.idle()
+                    last = dict(live=ln.live, obs=ln.o.obs(), off=off, veh=veh, loc=ln.o.vehicles()["loc"], outc=ln.outc)
+                if a["acts"] is not None:
+                    todo = [x for x in a["acts"][r] if x[0] >= 0]
+                    if todo and not ln.live:
+                        self.expect_err = True
+                        self.stats["hook_refused"] += 1
+                    elif todo:
+                        off, veh = ln.idle()
+                        vs, ts = [], []
+                        for cl, _, tg in todo:
+                            if off[cl + 1] > off[cl]:
+                                vs.append(int(veh[off[cl]])); ts.append(int(tg))
+                                self.stats["hook_applied"] += 1
+                            else:
+                                self.expect_err = True
+                                self.stats["hook_refused"] += 1
+                        if vs:
+                            ln.dispatch(vs, ts)
+                ln.advance()
+            seen.append(last)
+        self.t += n
+        self.settle()
+        got = to_host(blk)
+        for r, s in enumerate(seen):
+            if s["live"]:
+                for i, name in enumerate(PLANES):
+                    if pl & (1 << i):
+                        np.testing.assert_array_equal(got[i, r], s["obs"][name], err_msg="run_hooked: plane %s of replica %d at the last slot" % (name, r))
+            if outc is not None:
+                np.testing.assert_array_equal(to_host(outc)[:, r, :].T, s["outc"], err_msg="run_hooked: outcomes of replica %d at the last slot" % r)
+            if heads is not None:
+                hv, hn = expected_heads(c, s["off"], s["veh"], s["loc"], a["L"])
+                h = to_host(heads)
+                np.testing.assert_array_equal(h[0, r], hv, err_msg="run_hooked: head vehicles of replica %d" % r)
+                np.testing.assert_array_equal(h[1, r], hn, err_msg="run_hooked: head nodes of replica %d" % r)
+
+    def restore(self, kind, a):
+        env, c, st = self.env, self.c, self.stats
+        state = self.snap_state if self.snap is not None else VOID
+        st["restores"] += 1
+        st["restores_" + state.lower()] += 1
+        if self.stepped and self.dispatched_in_slot:
+            st["restore_after_dispatch"] += 1
+
+        def call():
+            if kind == "restore_torch":
+                held = to_device(env, np.asarray(a["src"], dtype=np.int32))
+                env.restore_torch(held)
+                env.sync()
+            else:
+                env.restore(a["src"])
+        if a["expect"] is not None:
+            self.refused(a["expect"], call)          # (a refused restore changes nothing: the checks below say so)
+            if state == VALID:
+                st["restores_valid_ok"] += 1
+                st["refused_map_day" if "order days" in a["expect"] else "refused_map_range"] += 1
+            return True
+        if state == UNKNOWN:
+            try:
+                call()
+            except Exception as e:
+                assert re.search(NO_SNAPSHOT, str(e)), e
+                self.snap, self.snap_state = None, VOID
+                assert env.snapshot_info() is None
+                return True
+            self.snap_state = VALID
+            st["restore_none_ok"] += a["src"] is None
+        else:
+            call()
+            st["restores_valid_ok"] += 1
+            st["restore_none_ok"] += a["src"] is None
+        src = np.arange(c.R) if a["src"] is None else np.asarray(a["src"])
+        rows = self.snap["rows"]
+        self.lines = [Lineage(c, rows[s][0], rows[s][1], rows[s][2]) for s in src]
+        self.t, self.stepped = self.snap["t"], self.snap["stepped"]
+        self.dispatched_in_slot = bool(self.stepped and any(self.t in ln.acts for ln in self.lines))
+        self.expect_err = False
+        return True
+
+    # ---- comparisons ----------------------------------------------------------------------------------------------------------
+    def check(self, full):
+        """Clock, all eight counters and the idle_now / inflight planes of every replica; ``full``: everything check_state of
+        tests/test_gpu_snapshot.py compares - all planes of a stepped slot, container order, per-vehicle view, per-order results."""
+        env = self.env
+        assert env.clock[0] == self.t, "clock: engine %d, model %d" % (env.clock[0], self.t)
+        cn, ob = env.counters(), env.obs()
+        od = env.orders() if full else None
+        for r, ln in enumerate(self.lines):
+            oc, oo = ln.o.counters(), ln.o.obs()
+            for i, k in enumerate(COUNTERS):
+                assert cn[r, i] == oc[k], "replica %d counter %s: engine %d, model %d" % (r, k, cn[r, i], oc[k])
+            planes = PLANES if (full and ln.stepped and ln.live) else ("idle_now", "inflight")
+            for k in planes:
+                np.testing.assert_array_equal(ob[k][r], oo[k], err_msg="replica %d plane %s" % (r, k))
+            if full:
+                check_lists(env, r, ln.o, ln.t)
+                res = ln.o.orders()
+                n = res["status"].size
+                for k in ("status", "vehicle", "wait"):
+                    np.testing.assert_array_equal(od[k][r][:n], res[k], err_msg="replica %d orders %s" % (r, k))
+        if full and self.sup is not None and self.stepped:
+            ring, slot = self.sup
+            np.testing.assert_array_equal(to_host(ring[int(to_host(slot)[0])]), ob["supply"], err_msg="supply in place")
+
+    def read(self, kind, a):
+        env, c, lines = self.env, self.c, self.lines
+        st_live = [ln.stepped and ln.live for ln in lines]
+        if kind in ("obs", "obs_torch", "obs_inplace"):
+            if kind == "obs":
+                got, names = env.obs(), PLANES
+            elif kind == "obs_torch":
+                pl = a["planes"]
+                blk = env.obs_torch(**{n: bool(pl & (1 << i)) for i, n in enumerate(PLANES)})
+                env.sync()
+                blk = to_host(blk)
+                names = [n for i, n in enumerate(PLANES) if pl & (1 << i)]
+                got = {n: blk[PLANES.index(n)] for n in names}
+            else:
+                try:
+                    views = env.obs_inplace_torch()
+                except Exception as e:      # (documented for regrouped storage: more than one order day resident)
+                    assert len(self.days) > 1 and "regrouped by order day" in str(e), e
+                    return
+                env.sync()
+                got = {n: to_host(v) for n, v in views.items()}
+                names = list(got)
+            for r, ln in enumerate(lines):
+                oo = ln.o.obs()
+                for n in names:
+                    if st_live[r] or n in ("idle_now", "inflight"):
+                        np.testing.assert_array_equal(got[n][r], oo[n], err_msg="%s: replica %d plane %s" % (kind, r, n))
+        elif kind in ("counters", "total_counters"):
+            exp = np.array([[ln.o.counters()[k] for k in COUNTERS] for ln in lines], dtype=np.int64)
+            if kind == "counters":
+                np.testing.assert_array_equal(env.counters(), exp)
+            else:
+                np.testing.assert_array_equal(env.total_counters()[:6], exp[:, :6].sum(axis=0))
+        elif kind == "orders":
+            od = env.orders()
+            for r, ln in enumerate(lines):
+                res = ln.o.orders()
+                for k in ("status", "vehicle", "wait"):
+                    np.testing.assert_array_equal(od[k][r][:res[k].size], res[k], err_msg="orders: replica %d %s" % (r, k))
+        elif kind in ("lists", "vehicles"):
+            check_lists(env, a["r"], lines[a["r"]].o, self.t)
+        elif kind == "idle_heads":
+            got = env.idle_heads(a["L"])
+            for r, ln in enumerate(lines):
+                off, veh = ln.idle()
+                hv, hn = expected_heads(c, off, veh, ln.o.vehicles()["loc"], a["L"])
+                np.testing.assert_array_equal(got["veh"][r], hv, err_msg="idle_heads: replica %d vehicles" % r)
+                np.testing.assert_array_equal(got["node"][r], hn, err_msg="idle_heads: replica %d nodes" % r)
+        elif kind == "outcomes":
+            got = env.outcomes()
+            for r, ln in enumerate(lines):
+                for i, n in enumerate(("served", "rejected", "wait_sum", "value_sum")):
+                    np.testing.assert_array_equal(got[n][r], ln.outc[:, i], err_msg="outcomes: replica %d %s" % (r, n))
+
+    def finish(self):
+        """The final full comparison, once the open day has been finished by logged calls of ``next``."""
+        self.check(True)
+        self.stats["calls"].append(self.n_calls)
+        self.done = True
+        self.close()
+
+
+def corpus():
+    """(seeds of the single-handle cases, seed pairs of the two-handle cases) of the GPU corpus; VDS_APISEQ_N: more single ones."""
+    return list(range(int(os.environ.get("VDS_APISEQ_N", "32")))), [(1000 + 2 * i, 1001 + 2 * i) for i in range(8)]
+
+
+def expected_heads(c, off, veh, loc, L):
+    hv = np.full((c.C, L), -1, dtype=np.int32)
+    hn = np.full((c.C, L), -1, dtype=np.int32)
+    for cl in range(c.C):
+        n = min(int(off[cl + 1] - off[cl]), L)
+        hv[cl, :n] = veh[off[cl]:off[cl] + n]
+        hn[cl, :n] = loc[hv[cl, :n]]
+    return hv, hn
+
+
+def run_script(env_factory, seed, upto=None, stats=None, stream=None):
+    """The script of ``seed`` on a handle made by ``env_factory`` (the signature of ``BatchedDispatchEnv``); ``upto``: only its first
+    ``upto`` calls.  Returns the Script (its ``log`` holds the calls, its ``stats`` what they covered)."""
+    s = Script(env_factory, seed, stream=stream, stats=stats)
+    try:
+        while s.next(upto):
+            pass
+    finally:
+        s.close()
+    return s
