@@ -394,7 +394,9 @@ int vds_reduce_counters_into(vds_handle *h, void *dev_out);
 
 /* Per-order results of replicas [r0, r0+nr): status uint8 (0 never processed - quirk Q1 :914-915,
  * 1 matched, 2 "Reject"), vehicle int32 (index into Vehicles or -1), wait int32
- * (Order.PickupWaitTime, -1 if none); each [nr*O], order-id-major per replica; NULL to skip. */
+ * (Order.PickupWaitTime, -1 if none); each [nr*O], order-id-major per replica; NULL to skip.  Every element of an array that is
+ * passed is written: with order days per replica O is the longest day's order count, and a shorter day's row reads status 0,
+ * vehicle -1, wait -1 past its own orders - as does an order that has not been processed (yet). */
 int vds_read_orders(vds_handle *h, int32_t r0, int32_t nr, uint8_t *status, int32_t *vehicle, int32_t *wait);
 
 /* Container views of one replica, in the reference's container order:
@@ -402,7 +404,8 @@ int vds_read_orders(vds_handle *h, int32_t r0, int32_t nr, uint8_t *status, int3
  *     vehicle's LocationNode;
  *   arr_off [C+1], arr_veh [V], arr_min [V], arr_order [V], arr_node [V]:
  *     Cluster.VehiclesArrivetime in dict insertion order: vehicle, arrival minute, carried
- *     order id (-1 = dispatched, no order) and DeliveryPoint.  NULL to skip a group. */
+ *     order id (-1 = dispatched, no order) and DeliveryPoint.  NULL to skip a group.
+ * Every element of an array that is passed is written: the [V] arrays hold -1 from position idle_off[C] / arr_off[C] on. */
 int vds_read_lists(vds_handle *h, int32_t replica, int32_t *idle_off, int32_t *idle_veh, int32_t *idle_node,
                    int32_t *arr_off, int32_t *arr_veh, int32_t *arr_min, int32_t *arr_order, int32_t *arr_node);
 
@@ -413,7 +416,8 @@ int vds_read_lists(vds_handle *h, int32_t replica, int32_t *idle_off, int32_t *i
  *   cluster    the cluster whose idle list / arrival dict holds the vehicle (for a vehicle on the way: the
  *              destination's cluster.  The reference leaves Vehicle.LocationNode / .Cluster at the trip origin
  *              until ArriveVehicleUpDate, objects.py:84-89; the origin is not kept on the device);
- *   arrive_min arrival minute on the day clock (-1 when idle);  order  carried Order.ID (-1 when none). */
+ *   arrive_min arrival minute on the day clock (-1 when idle);  order  carried Order.ID (-1 when none).
+ * Every element of an array that is passed is written. */
 int vds_read_vehicles(vds_handle *h, int32_t replica, uint8_t *state, int32_t *node, int32_t *cluster,
                       int32_t *arrive_min, int32_t *order);
 
@@ -469,7 +473,7 @@ int32_t vds_version(void);
  * csrc/ (the .hip kernel files, vds_kernels_common.h, vds_device.h) and the first 8 of the sha1 over the host side (vds_api.hip,
  * vds.h); `make -C vehicles_dispatch_simulator_amd/csrc srchash` prints the same for a checkout, `make kernelhash` the kernel half
  * (what the committed rocprofv3 figures are keyed by: they survive host-only edits).  Instrumented builds append "+prof" / "+dbg" /
- * "+canary".  bench.py prints it and compares it with the build the
+ * "+canary" / "+dirty".  bench.py prints it and compares it with the build the
  * committed rocprofv3 figures (profiles/traffic.json, limiter.json) were measured on.  Static string. */
 const char *vds_build_id(void);
 

@@ -42,6 +42,11 @@ int vds_debug_check_guards(vds_handle *h);
 /* guarded build only: damages one guard zone on purpose (the test of the check); VDS_EINVAL in other builds */
 int vds_debug_poke_guard(vds_handle *h);
 
+/* dirty build (make dirty: every byte the library obtains for a handle is filled with the byte VDS_DIRTY_FILL names, hex, default
+ * A5, before first use): a 4-int device table taken through the library's allocator and copied back as handed out - four words of the
+ * fill byte; VDS_ESTATE in every other build */
+int vds_debug_dirty_probe(vds_handle *h, int32_t out[4]);
+
 /* executable day graphs kept past their handle: always 0 (day graphs are single chains, destroyed with their handle) */
 int vds_debug_graph_pool_size(void);
 

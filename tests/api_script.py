@@ -20,7 +20,13 @@ Calls that the header makes illegal are never drawn: after a load, ``set_replica
 load / map / cap / ``set_run_groups`` or a restore that must be refused (state VOID) may follow, until a reset has been issued -
 ``reset_again`` only after ``set_idle_cap`` (the start nodes may not survive a load or another map).  A restore right behind
 ``set_idle_cap`` is drawn in state UNKNOWN too: a cap that replaced no table keeps the snapshot, so either "no snapshot" or the
-snapshot's state is the answer; the reset that the header asks for follows all the same."""
+snapshot's state is the answer; the reset that the header asks for follows all the same.
+
+``record=`` (a list; default off): the TRANSCRIPT of a script - after every call that leaves an episode to read, a digest of the
+complete arrays every read entry point returns (``record_state``), whether the model has an opinion on them or not.  Two runs of
+one seed on one engine must give the same transcript whatever the engine's memory held before (tests/test_gpu_dirty_memory.py);
+recording draws nothing from the generator, so the calls are those of the unrecorded script."""
+import hashlib
 import os
 import random
 import re
@@ -221,11 +227,38 @@ class ScriptFailure(AssertionError):
     pass
 
 
+RECORD_HEADS_L = 4              # list positions of the idle-heads block a transcript reads
+
+
+def digest(v):
+    """sha1 over everything a read returned: arrays with dtype and shape and all their bytes, containers in key order."""
+    h = hashlib.sha1()
+
+    def feed(x):
+        if isinstance(x, dict):
+            for k in sorted(x):
+                h.update(("{%s}" % k).encode())
+                feed(x[k])
+        elif isinstance(x, (tuple, list)):
+            h.update(b"(%d)" % len(x))
+            for y in x:
+                feed(y)
+        elif x is None or isinstance(x, (bool, int, str)):
+            h.update(repr(x).encode())
+        else:
+            a = np.ascontiguousarray(to_host(x))
+            h.update(("[%s %s]" % (a.dtype.str, a.shape)).encode())
+            h.update(a.tobytes())
+    feed(v)
+    return h.hexdigest()[:16]
+
+
 class Script:
     """One handle, its model and the generator of its calls.  ``next()`` draws, issues and checks one call; False when the script is
     over (the open day has then been finished and compared in full)."""
 
-    def __init__(self, env_factory, seed, stream=None, stats=None):
+    def __init__(self, env_factory, seed, stream=None, stats=None, record=None):
+        self.record = record
         self.c = c = case(seed)
         self.seed, self.factory, self.stream = seed, env_factory, stream
         self.rng = np.random.default_rng(40_000 + seed)
@@ -565,6 +598,8 @@ class Script:
                 kind, a = self.draw()
             self.log.append("%3d %s(%s)" % (self.n_calls, kind, ", ".join("%s=%s" % (k, show(v)) for k, v in a.items())))
             self.issue(kind, a)
+            if self.record is not None and self.lines is not None and not self.need_reset:
+                self.record_state(kind)
             self.n_calls += 1
         except ScriptFailure:
             raise
@@ -923,6 +958,49 @@ class Script:
                 for i, n in enumerate(("served", "rejected", "wait_sum", "value_sum")):
                     np.testing.assert_array_equal(got[n][r], ln.outc[:, i], err_msg="outcomes: replica %d %s" % (r, n))
 
+    def record_state(self, kind):
+        """Appends "<call> <kind> <read> <digest>" for every read entry point, each array in full.  Nothing is masked: every plane of
+        the observation block is asked for (include/vds.h leaves only planes NOT asked for unspecified)."""
+        env, c = self.env, self.c
+
+        def put(name, v):
+            self.record.append("%d %s %s %s" % (self.n_calls, kind, name, digest(v)))
+        put("clock", tuple(env.clock))
+        put("snapshot_info", env.snapshot_info())
+        put("obs", env.obs())
+        put("counters", env.counters())
+        put("orders", env.orders())
+        put("outcomes", env.outcomes())
+        put("idle_heads", env.idle_heads(RECORD_HEADS_L))
+        for r in range(c.R):
+            put("lists[%d]" % r, env.lists(r))
+            put("vehicles[%d]" % r, env.vehicles(r))
+        # the device planes, read back in full
+        blk = env.obs_torch()
+        env.sync()
+        put("obs_torch", blk)
+        try:
+            views = env.obs_inplace_torch()
+        except Exception as e:          # (documented for regrouped storage)
+            assert "regrouped by order day" in str(e), e
+            views = None
+        if views is not None:
+            env.sync()
+        put("obs_inplace_torch", views)
+        blk = env.outcomes_torch()
+        env.sync()
+        put("outcomes_torch", blk)
+        blk = env.idle_heads_torch(RECORD_HEADS_L)
+        env.sync()
+        put("idle_heads_torch", blk)
+        if hasattr(env, "counters_torch"):
+            blk = env.counters_torch()
+            env.sync()
+            put("counters_torch", blk)
+        if self.sup is not None:
+            env.sync()
+            put("supply_inplace_torch", tuple(self.sup))
+
     def finish(self):
         """The final full comparison, once the open day has been finished by logged calls of ``next``."""
         self.check(True)
@@ -946,10 +1024,11 @@ def expected_heads(c, off, veh, loc, L):
     return hv, hn
 
 
-def run_script(env_factory, seed, upto=None, stats=None, stream=None):
+def run_script(env_factory, seed, upto=None, stats=None, stream=None, record=None):
     """The script of ``seed`` on a handle made by ``env_factory`` (the signature of ``BatchedDispatchEnv``); ``upto``: only its first
-    ``upto`` calls.  Returns the Script (its ``log`` holds the calls, its ``stats`` what they covered)."""
-    s = Script(env_factory, seed, stream=stream, stats=stats)
+    ``upto`` calls; ``record``: a list that receives the script's transcript (module docstring).  Returns the Script (its ``log``
+    holds the calls, its ``stats`` what they covered)."""
+    s = Script(env_factory, seed, stream=stream, stats=stats, record=record)
     try:
         while s.next(upto):
             pass

@@ -490,3 +490,33 @@ def test_a_prefix_replays_the_same_calls():
     whole = run_script(OracleEnv, seed)
     part = run_script(OracleEnv, seed, upto=20)
     assert part.n_calls == 20 and [l for l in part.log if not l.startswith("    --")] == [l for l in whole.log if not l.startswith("    --")][:20]
+
+
+RECORDED_READS = ("clock", "snapshot_info", "obs", "counters", "orders", "outcomes", "idle_heads", "lists[0]", "vehicles[0]", "obs_torch",
+                  "obs_inplace_torch", "outcomes_torch", "idle_heads_torch")
+
+
+@pytest.mark.parametrize("seed", corpus_seeds()[:3])
+def test_a_recorded_script_is_deterministic_and_draws_the_same_calls(seed):
+    """``record=`` on the stand-in engine: two runs give the same transcript, every read entry point is in it after every call that
+    leaves an episode to read, and the calls are those of the unrecorded script (recording draws nothing from the generator)."""
+    one, two = [], []
+    a = run_script(OracleEnv, seed, record=one)
+    b = run_script(OracleEnv, seed, record=two)
+    plain = run_script(OracleEnv, seed)
+    assert one and one == two
+    assert a.log == plain.log == b.log and a.n_calls == plain.n_calls
+    calls = {}
+    for line in one:
+        n, kind, name, dig = line.split()
+        calls.setdefault(int(n), set()).add(name)
+        assert len(dig) == 16
+    assert len(calls) >= 30, len(calls)
+    R = a.c.R
+    for n, names in calls.items():
+        assert set(RECORDED_READS) <= names and "lists[%d]" % (R - 1) in names and "vehicles[%d]" % (R - 1) in names, (n, sorted(names))
+    # a digest covers every element: one changed value, another digest
+    x = np.arange(12, dtype=np.int32).reshape(3, 4)
+    y = x.copy()
+    y[2, 3] += 1
+    assert api_script.digest(dict(a=x)) != api_script.digest(dict(a=y)) and api_script.digest(x) != api_script.digest(x.reshape(4, 3))

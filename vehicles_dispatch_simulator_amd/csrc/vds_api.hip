@@ -31,6 +31,33 @@ using namespace vds;
 
 static thread_local std::string g_create_error;
 
+// Dirty build (make dirty, -DVDS_DIRTY): every byte the library obtains for a handle - device tables from dev_alloc (fresh, or a
+// block of the day before out of order_cache), the device copies of Static / State, pinned staging and the blocks of PinnedPool
+// (fresh, recycled, or ordinary memory) - is filled with one byte before first use: what a long-lived process gets from hipMalloc
+// after it has used the memory before.  A result that depends on a table's prior content then differs from the oracle's (and
+// between two fill bytes: VDS_DIRTY_FILL, a hex byte, default A5 - 0xA5A5A5A5 is a negative count, 0x5A5A5A5A a positive one).
+// The fill is synchronous: nothing runs beside it.  Every other build: the two macros are empty.
+#ifdef VDS_DIRTY
+static int dirty_byte() {
+    static const int b = [] {
+        const char *v = getenv("VDS_DIRTY_FILL");
+        char *end = nullptr;
+        const unsigned long x = (v && *v) ? strtoul(v, &end, 16) : 0xA5;
+        return (v && *v && (*end || x > 0xFF)) ? 0xA5 : (int)x;
+    }();
+    return b;
+}
+static void dirty_dev(void *p, size_t bytes) {
+    (void)hipMemset(p, dirty_byte(), bytes);
+    (void)hipDeviceSynchronize();
+}
+#define VDS_DIRTY_HOST(p, bytes) memset((p), dirty_byte(), (bytes))
+#define VDS_DIRTY_DEV(p, bytes) dirty_dev((p), (bytes))
+#else
+#define VDS_DIRTY_HOST(p, bytes) ((void)0)
+#define VDS_DIRTY_DEV(p, bytes) ((void)0)
+#endif
+
 // the largest host tables of a load in PINNED host memory (the sorted order records, the arrival-slot records and indices: 90 MB at 16 days,
 // uploaded at ~5 GB/s from pageable memory - 18 of a 16-day load's 50 ms - and at the link's rate from pinned).  Page-locking costs
 // milliseconds per block, so blocks are pooled per process and handed out again (a Reload asks for the same sizes); a block that
@@ -50,13 +77,15 @@ struct PinnedPool {
             void *p = idle[best].first; const size_t b = idle[best].second;
             idle.erase(idle.begin() + best); idle_bytes -= b;
             live[p] = {b, true};
+            VDS_DIRTY_HOST(p, b);
             return p;
         }
         void *p = nullptr;
-        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess && p) { live[p] = {bytes, true}; return p; }
+        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess && p) { live[p] = {bytes, true}; VDS_DIRTY_HOST(p, bytes); return p; }
         (void)hipGetLastError();
         p = ::operator new(bytes);
         live[p] = {bytes, false};
+        VDS_DIRTY_HOST(p, bytes);
         return p;
     }
     void put(void *p) {
@@ -316,6 +345,7 @@ static int dev_alloc(vds_handle *h, T **p, size_t n) {
             h->order_bytes[(void *)*p] = h->order_cache[best].second;
             h->order_cache.erase(h->order_cache.begin() + best);
             h->order_allocs.push_back((void *)*p);
+            VDS_DIRTY_DEV((void *)*p, h->order_bytes[(void *)*p]);
             return VDS_OK;
         }
     }
@@ -329,6 +359,7 @@ static int dev_alloc(vds_handle *h, T **p, size_t n) {
         g_guards[(void *)(base + GUARD_FRONT)] = GuardRec{(void *)base, bytes};
     }
     *p = reinterpret_cast<T *>(base + GUARD_FRONT);
+    VDS_DIRTY_DEV((void *)*p, bytes);
     (h->alloc_sink ? *h->alloc_sink : h->dev_allocs).push_back((void *)*p);
     if (!GUARDED && h->alloc_sink == &h->order_allocs) h->order_bytes[(void *)*p] = bytes;
     return VDS_OK;
@@ -483,6 +514,8 @@ static int dev_copy_sync(vds_handle *h) {
     if (!h->d_S) {
         HIPCHK(h, hipMalloc((void **)&h->d_S, sizeof(Static)));
         HIPCHK(h, hipMalloc((void **)&h->d_D, sizeof(State)));
+        VDS_DIRTY_DEV(h->d_S, sizeof(Static));
+        VDS_DIRTY_DEV(h->d_D, sizeof(State));
     }
     h->S.self_dev = h->d_S; h->S.state_dev = h->d_D;
     Static want = h->S;
@@ -530,6 +563,8 @@ const char *vds_build_id(void) {
     return "src:" VDS_SRC_HASH "+dbg";
 #elif defined(VDS_CANARY)
     return "src:" VDS_SRC_HASH "+canary";
+#elif defined(VDS_DIRTY)
+    return "src:" VDS_SRC_HASH "+dirty";
 #else
     return "src:" VDS_SRC_HASH;
 #endif
@@ -1289,6 +1324,7 @@ static bool request_counters(vds_handle *h) {
         if (hipHostMalloc((void **)&f.pin_slow, sizeof(int)) != hipSuccess || hipEventCreateWithFlags(&f.ev, hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError(); return false;
         }
+        VDS_DIRTY_HOST(f.pin_slow, sizeof(int));
         *f.pin_slow = 0;
     }
     if (!h->have_reset || h->t <= 0) return true;
@@ -1299,7 +1335,7 @@ static bool request_counters(vds_handle *h) {
         const size_t words = (size_t)S.T * S.C;          // (the plane's rows of this day: within [slow_tick_cap][C])
         if (f.pin_tick_cap < words) {
             if (f.pin_tick) { (void)hipStreamSynchronize(h->stream); (void)hipHostFree(f.pin_tick); f.pin_tick = nullptr; f.pin_tick_cap = 0; }
-            if (hipHostMalloc((void **)&f.pin_tick, words * sizeof(int)) == hipSuccess) f.pin_tick_cap = words;
+            if (hipHostMalloc((void **)&f.pin_tick, words * sizeof(int)) == hipSuccess) { f.pin_tick_cap = words; VDS_DIRTY_HOST(f.pin_tick, words * sizeof(int)); }
             else { (void)hipGetLastError(); f.pin_tick = nullptr; }
         }
         f.ticks_valid = f.pin_tick && hipMemcpyAsync(f.pin_tick, h->D.slow_tick, words * sizeof(int), hipMemcpyDeviceToHost, h->stream) == hipSuccess;
@@ -1987,6 +2023,7 @@ static int snap_alloc(vds_handle *h) {
             snap_free(h);
             return fail(h, VDS_ENOMEM, "vds_snapshot: no pinned host memory for the restore map");
         }
+    for (int i = 0; i < 2; ++i) VDS_DIRTY_HOST(s.pin_map[i], (size_t)S.R * sizeof(int));
     s.bytes = (long long)bytes;
     return VDS_OK;
 }
@@ -2491,6 +2528,10 @@ static int read_lists_impl(vds_handle *h, int32_t replica, int32_t *idle_off, in
             }
             idle_off[c + 1] = n;
         }
+        for (int k = n; k < S.V; ++k) {      // past the last list: -1 (vds.h)
+            idle_veh[k] = -1;
+            if (idle_node) idle_node[k] = -1;
+        }
     }
     if (want_arr) {
         // parity holding far posts not yet drained; a replica whose day is over stopped at ITS last tick
@@ -2588,6 +2629,12 @@ static int read_lists_impl(vds_handle *h, int32_t replica, int32_t *idle_off, in
             }
             arr_off[c + 1] = n;
         }
+        for (int k = n; k < S.V; ++k) {      // past the last dict: -1 (vds.h)
+            arr_veh[k] = -1;
+            if (arr_min) arr_min[k] = -1;
+            if (arr_order) arr_order[k] = -1;
+            if (arr_node) arr_node[k] = -1;
+        }
     }
     return VDS_OK;
 }
@@ -2645,6 +2692,29 @@ int vds_debug_poke_guard(vds_handle *h) {
     if (it == g_guards.end()) return VDS_EINVAL;
     HIPCHK(h, hipMemset((char *)it->second.base + GUARD_FRONT + it->second.bytes + 5, 0, 1));
     return VDS_OK;
+}
+
+// Dirty build only (make dirty): a 4-int table taken through dev_alloc and copied back as it was handed out - the fill byte four
+// times over, which is the proof that the fill is live.  Other builds: VDS_ESTATE.
+int vds_debug_dirty_probe(vds_handle *h, int32_t out[4]) {
+    if (!h || !out) return VDS_EINVAL;
+#ifdef VDS_DIRTY
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int *p = nullptr;
+    std::vector<void *> mine;
+    int rc;
+    {
+        AllocInto into(h, &mine);
+        rc = dev_alloc(h, &p, (size_t)4);
+    }
+    if (rc) return rc;
+    const hipError_t e = hipMemcpy(out, p, 4 * sizeof(int), hipMemcpyDeviceToHost);
+    dev_free(p);
+    if (e != hipSuccess) return fail(h, VDS_EHIP, "vds_debug_dirty_probe: copying the table back failed: %s", hipGetErrorString(e));
+    return VDS_OK;
+#else
+    return fail(h, VDS_ESTATE, "vds_debug_dirty_probe: not a dirty build (make dirty)");
+#endif
 }
 
 // instrumented build: launch spans of k_tick_dense ([2 chains][256 slots]{first wavefront in, last out} on the 100 MHz s_memtime
