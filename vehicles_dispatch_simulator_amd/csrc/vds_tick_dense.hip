@@ -22,8 +22,8 @@
 // that say "slot t" in the row's LDS table, packed (ballot rank inside the lane group); dispatched vehicles (hooks) come through
 // the ring.  The slot's arrivals are ranked among themselves by their 32-bit dict-insertion keys and appended behind the list IN
 // LDS: the lanes write their loaded chunks and the ranked arrivals into the row's table and read the merged chunks back, so no
-// per-slot select is needed.  After the loop the survivors are packed into the same table (order preserved, :963) and written
-// back with 16-byte stores from the first changed chunk on.
+// per-slot select is needed.  The results read the winners' entries from that table (one LDS read per order); then the survivors
+// are packed into it (order preserved, :963) and written back with 16-byte stores from the first changed chunk on.
 // Order days: DM = 0 one shared day (bucket descriptors from Static.tdesc: one scalar load), 1 one day per workgroup, 2 one day per
 // ROW (every replica its own order stream).
 // Rows the tables cannot hold (> 128 / 256 entries, > 64 arrivals), rows with far arrivals and buckets with > 64 orders are
@@ -733,6 +733,10 @@ __device__ __forceinline__ void dense_body(const DenseArgs &S, const DenseArgs &
     constexpr int DEAD = sizeof(CT) == 1 ? 0xFF : DENSE_DEAD_COST;
     constexpr int PB = TS > 128 ? 8 : 7;        // bits of the list position inside a candidate key (cost << PB | position); 256-entry tables: byte costs only
     constexpr int PM = (1 << PB) - 1;
+    // results ahead of the compaction, the winners' entries read from the row's table: one shared day or one day per workgroup with
+    // byte costs.  The other forms (int costs, one day per row, stamp form) keep the compaction ahead of the results, which fetch the
+    // entries through the LDS crossbar: the other order costs them spilled VGPRs (profiles/r10_dense_tail)
+    constexpr bool TAIL = !ST && DM != 2 && sizeof(CT) == 1;
     static_assert(TS <= 128 || sizeof(CT) == 1, "256-entry tables need byte costs");
     const int lane = lane_id();
     const int lg = lane & (LPR - 1);
@@ -853,6 +857,17 @@ __device__ __forceinline__ void dense_body(const DenseArgs &S, const DenseArgs &
             const uint2 v = *reinterpret_cast<const uint2 *>(tab + lbase);
             e[0] = v.x; e[1] = v.y;
         }
+    } else if (TAIL) {
+        // no arrival in this wavefront: the chunks go into the row's table as they were loaded - the results read the winners' entries there
+        if (lbase < m) {
+            if (J >= 4) {
+#pragma unroll
+                for (int s = 0; s < J; s += 4) *reinterpret_cast<uint4 *>(tab + lbase + s) = make_uint4(e[s], e[s + 1], e[s + 2], e[s + 3]);
+            } else {
+                *reinterpret_cast<uint2 *>(tab + lbase) = make_uint2(e[0], e[1]);
+            }
+        }
+        wave_order();
     }
     PROF_STAMP(4);          // arrivals ranked, merged
     // packed loc bytes; slots at and behind position mnew are dead (loc byte = nc, the dead column)
@@ -921,8 +936,6 @@ __device__ __forceinline__ void dense_body(const DenseArgs &S, const DenseArgs &
         navail = mnew - h;
     }
     PROF_STAMP(6);          // match loop
-    // 6. order-preserving compaction of the survivors (:963) through the row's table, written back with whole-chunk stores from
-    //    the first changed position on
     int mfin = navail;
     if (ST) {
         // stamp form: nothing is removed.  The merged list goes back as it stands - from the first position the load-time packing or
@@ -946,7 +959,10 @@ __device__ __forceinline__ void dense_body(const DenseArgs &S, const DenseArgs &
             *reinterpret_cast<uint2 *>(tab + lbase) = make_uint2(0xFFFFu, 0xFFFFu);
         }
         wave_order();
-    } else {
+    }
+    // 6. order-preserving compaction of the survivors (:963) through the row's table, written back with whole-chunk stores from the
+    //    first changed position on.  TAIL: behind the results, which read the table first
+    auto compact = [&]() {
     int alive = 0, firstdead = IMAX;
 #pragma unroll
     for (int s = J - 1; s >= 0; --s) {
@@ -977,9 +993,12 @@ __device__ __forceinline__ void dense_body(const DenseArgs &S, const DenseArgs &
             *reinterpret_cast<uint2 *>(idle + lbase) = *reinterpret_cast<const uint2 *>(tab + lbase);
         }
     }
-    }
-    PROF_STAMP(7);          // compaction + write-back
-    // 7. results (:947-965): vehicle ids through the LDS crossbar, the arrival posts (ring-slot atomic, then the entry)
+    };
+    if (!ST && !TAIL) compact();
+    PROF_STAMP(7);          // compaction + write-back (TAIL: below)
+    // 7. results (:947-965).  TAIL: ahead of the compaction, which overwrites the row's table - the winner's entry is tab[position]
+    //    (the merged list is there in every case, step 4), one LDS read per order; else the entries come through the LDS crossbar, J
+    //    ds_bpermute per result round.  Then the arrival posts (ring-slot atomic, then the entry)
     int wsum = 0, vsum = 0, rej = 0;
     int2 *out_r = D.out + (size_t)r * S.Oq + (q0 - qb);
 #pragma unroll
@@ -996,10 +1015,13 @@ __device__ __forceinline__ void dense_body(const DenseArgs &S, const DenseArgs &
         const int wpos = rv & PM;
         const int src = (gbase + (wpos / J)) << 2;       // winner's entry: e[wpos % J] of group lane wpos / J
         unsigned went = 0;
+        if (TAIL) went = tab[wpos];
+        else {
 #pragma unroll
         for (int s = 0; s < J; ++s) {
             const unsigned got = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)e[s]);
             went = (wpos % J) == s ? got : went;
+        }
         }
         const int vid = matched ? (int)(went >> 8) : -1;
         if (has && !(abl & 8)) out_r[j] = make_int2(vid, matched ? wait : -1);
@@ -1052,6 +1074,8 @@ __device__ __forceinline__ void dense_body(const DenseArgs &S, const DenseArgs &
     wsum = grp_sum<LPR>(wsum);
     vsum = grp_sum<LPR>(vsum);
     rej = grp_sum<LPR>(rej);
+    PROF_STAMP(8);          // results, arrival slots
+    if (TAIL) { compact(); PROF_STAMP(7); }
     if (ST) {
         // the stamps of positions [0, mnew) (free behind the list, up to the old raw length: what a reader may look at), and the
         // replica's count of searching buckets whose orders outran the list: k_dfs_walk has work
