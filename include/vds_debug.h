@@ -47,6 +47,11 @@ int vds_debug_poke_guard(vds_handle *h);
  * fill byte; VDS_ESTATE in every other build */
 int vds_debug_dirty_probe(vds_handle *h, int32_t out[4]);
 
+/* device blocks of this process that the library holds, over all handles: out[0] their number, out[1] their bytes (guard zones not
+ * counted; blocks parked for the next load count).  A handle gives back what it took: the pair is the same before vds_create and after
+ * vds_destroy (tests/test_gpu_device_memory.py). */
+int vds_debug_device_blocks(int64_t out[2]);
+
 /* executable day graphs kept past their handle: always 0 (day graphs are single chains, destroyed with their handle) */
 int vds_debug_graph_pool_size(void);
 

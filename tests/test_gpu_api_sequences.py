@@ -1,20 +1,33 @@
 """Random API sequences on one handle against the oracle model (tests/api_script.py; its CPU half, with the coverage conditions of
 the corpus and the seeded faults, is tests/test_api_script_model.py): one case per seed on the real ``BatchedDispatchEnv`` - 32 by
 default, VDS_APISEQ_N for more - and 8 cases with TWO handles alive at once, each with its own case and model, their calls dealt
-alternately on one stream, the second handle closed and opened again half-way.  Bit-exact, no tolerance.  A red case names its seed,
+alternately on one stream, the second handle closed and opened again half-way.  Bit-exact, no tolerance.  A case that passed has also
+given back every device block its handles took (``vds_debug_device_blocks`` before the first handle and after the last close).  A red case names its seed,
 the failing call and the script so far; ``api_script.run_script(BatchedDispatchEnv, seed, upto=k)`` replays a prefix."""
+import ctypes
+import gc
 import statistics
 import time
+
+import numpy as np
 
 import pytest
 
 import api_script
 from api_script import Script, new_stats, run_script
-from vehicles_dispatch_simulator_amd import BatchedDispatchEnv
+from vehicles_dispatch_simulator_amd import BatchedDispatchEnv, _lib
 
 pytestmark = pytest.mark.gpu
 
 SINGLE, PAIRS = api_script.corpus()
+
+
+def device_blocks():
+    """(live device blocks of the process, their bytes); a handle some earlier test dropped without closing it is collected first"""
+    gc.collect()
+    out = np.zeros(2, dtype=np.int64)
+    assert _lib.load().vds_debug_device_blocks(out.ctypes.data_as(ctypes.c_void_p)) == 0
+    return int(out[0]), int(out[1])
 
 
 class Corpus:
@@ -25,6 +38,7 @@ class Corpus:
 
     def case(self, key):
         if key not in self.done:
+            before = device_blocks()
             stats, t0 = new_stats(), time.perf_counter()
             try:
                 if isinstance(key, tuple):
@@ -32,6 +46,7 @@ class Corpus:
                 else:
                     run_script(BatchedDispatchEnv, key, stats=stats)
                 self.done[key] = (time.perf_counter() - t0, stats)
+                assert device_blocks() == before, "device (blocks, bytes) %s after the case, %s before it" % (device_blocks(), before)
             except BaseException as e:
                 self.done[key] = e
         if isinstance(self.done[key], BaseException):

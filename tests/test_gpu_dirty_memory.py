@@ -20,7 +20,7 @@ byte before first use (``VDS_DIRTY_FILL``, hex, default ``A5``: ``0xA5A5A5A5`` i
 Seconds per leg under the PRODUCT library on an MI355X (one run each, pytest start-up included), from which the limits follow as
 ten times that + 120 s for the build check and start-up - a safety stop, not a measurement:
 
-    a 110   b 53   c 13   d 6   e 15   f 6   g 7
+    a 110   b 53   c 13   d 6   e 15   f 6   g 7   h 9
 
 The libraries are built on demand into ``build/`` exactly as tests/test_gpu_debug_builds.py does (content hashes, not file times)."""
 import json
@@ -50,6 +50,7 @@ LEGS = {
     "g": (7, ["test_gpu_replica_days.py", "test_gpu_idle_heads.py"],
           "(test_gpu_replica_days and (changes_every_episode or blocks_of_sixteen)) or "
           "(test_gpu_idle_heads and (layout or replica_days or interleaved_days or own_order_stream))"),
+    "h": (9, ["test_gpu_device_memory.py"], None),
 }
 # (leg, fill byte): every leg with the default byte, then the two that reach the most tables with the positive pattern
 RUNS = [(k, None) for k in LEGS] + [("a", "5A"), ("c", "5A")]

@@ -4,6 +4,7 @@
 #include "../../include/vds_debug.h"
 #include "vds_device.h"
 #include "vds_launch.h"
+#include "vds_mem.h"
 #include "vds_tables.h"
 
 #include <algorithm>
@@ -20,7 +21,6 @@
 #include <mutex>
 #include <new>
 #include <numeric>
-#include <optional>
 #include <string>
 #include <vector>
 #include <execinfo.h>
@@ -30,33 +30,6 @@
 using namespace vds;
 
 static thread_local std::string g_create_error;
-
-// Dirty build (make dirty, -DVDS_DIRTY): every byte the library obtains for a handle - device tables from dev_alloc (fresh, or a
-// block of the day before out of order_cache), the device copies of Static / State, pinned staging and the blocks of PinnedPool
-// (fresh, recycled, or ordinary memory) - is filled with one byte before first use: what a long-lived process gets from hipMalloc
-// after it has used the memory before.  A result that depends on a table's prior content then differs from the oracle's (and
-// between two fill bytes: VDS_DIRTY_FILL, a hex byte, default A5 - 0xA5A5A5A5 is a negative count, 0x5A5A5A5A a positive one).
-// The fill is synchronous: nothing runs beside it.  Every other build: the two macros are empty.
-#ifdef VDS_DIRTY
-static int dirty_byte() {
-    static const int b = [] {
-        const char *v = getenv("VDS_DIRTY_FILL");
-        char *end = nullptr;
-        const unsigned long x = (v && *v) ? strtoul(v, &end, 16) : 0xA5;
-        return (v && *v && (*end || x > 0xFF)) ? 0xA5 : (int)x;
-    }();
-    return b;
-}
-static void dirty_dev(void *p, size_t bytes) {
-    (void)hipMemset(p, dirty_byte(), bytes);
-    (void)hipDeviceSynchronize();
-}
-#define VDS_DIRTY_HOST(p, bytes) memset((p), dirty_byte(), (bytes))
-#define VDS_DIRTY_DEV(p, bytes) dirty_dev((p), (bytes))
-#else
-#define VDS_DIRTY_HOST(p, bytes) ((void)0)
-#define VDS_DIRTY_DEV(p, bytes) ((void)0)
-#endif
 
 // the largest host tables of a load in PINNED host memory (the sorted order records, the arrival-slot records and indices: 90 MB at 16 days,
 // uploaded at ~5 GB/s from pageable memory - 18 of a 16-day load's 50 ms - and at the link's rate from pinned).  Page-locking costs
@@ -118,6 +91,18 @@ struct PinnedAlloc {
 template <typename T> using pvec = std::vector<T, PinnedAlloc<T>>;
 
 
+// Device memory of a handle: every block belongs to one of these groups, named where it is allocated (dev_alloc / upload); vds_destroy frees them all
+enum Mem {
+    MEM_STATIC,                          // static tables, scratch, the device copies of Static / State
+    MEM_ORDERS,                          // tables of the loaded day (parked by the next vds_load_orders* for its own tables, DevGroup::recycle)
+    MEM_MAP,                             // the replica -> day map's device arrays (replaced by vds_set_replica_days / the next load)
+    MEM_RESULTS,                         // per-replica result tables out / arr / slog (sized by S.R)
+    MEM_STATE,                           // per-replica state (kept across days while the capacities still fit), with d_outc and d_heads
+    MEM_IDLE,                            // the idle table alone (regrown by vds_reset / vds_set_idle_cap)
+    MEM_SNAP,                            // the snapshot store
+    MEM_GROUPS
+};
+
 struct vds_handle {
     vds_config cfg{};
     Static S{};
@@ -171,23 +156,13 @@ struct vds_handle {
     int R_ext = 0;                       // vds_config.replicas
     std::vector<int> int2ext, ext2int;
     int alloc_R = 0;                     // replica count the state tables were allocated for
-    std::vector<void *> dev_allocs;          // static tables, scratch
-    std::vector<void *> order_allocs;        // tables of the loaded day (replaced by the next vds_load_orders)
-    // blocks of the day before, handed out again to the next load's tables of about the same size (a Reload replaces ~20 tables; hipFree +
-    // hipMalloc of the large ones took 1 ms or 80 ms from one call to the next: profiles/r05/load_timing_results_tables.txt); what a load
-    // does not take again is freed when it ends.  Not in the guarded build (a reused block's guard would not sit behind the table).
-    std::unordered_map<void *, size_t> order_bytes;
-    std::vector<std::pair<void *, size_t>> order_cache;
-    std::vector<void *> map_allocs;          // the replica -> day map's device arrays (replaced by vds_set_replica_days / the next load)
-    std::vector<void *> result_allocs;       // per-replica result tables out / arr / slog (sized by S.R)
+    DevGroup mem[MEM_GROUPS];
+    vds_handle() { mem[MEM_ORDERS].recycle = true; }
     std::vector<DayDesc> ddesc_host;         // the loaded days (+ the empty day of padding replicas, last)
     size_t res_cap_out = 0, res_cap_arr = 0, res_cap_slog = 0;      // elements the result tables (alloc_results) were allocated for
     int alloc_O = 0;                         // what alloc_state was sized for (orders per day)
     int Oqmax = 0;
-    std::vector<void *> state_allocs;        // per-replica state (kept across days while the capacities still fit)
-    std::vector<void *> idle_allocs;         // the idle table alone (regrown by vds_reset / vds_set_idle_cap)
     int idle_cap_grown = 0;                  // capacity chosen by a reset histogram or vds_set_idle_cap (0: none)
-    std::vector<void *> *alloc_sink = nullptr;
     // device scratch
     int *d_veh_node = nullptr;
     unsigned long long *d_seeds = nullptr;   // vds_reset_random: the replicas' seeds, the fullest start list per replica
@@ -200,12 +175,11 @@ struct vds_handle {
     int *d_veh_stage = nullptr;              // vds_reset: the caller's start nodes land here and are checked on the device before they
     unsigned long long *d_bad = nullptr;     // replace d_veh_node (index of the first node outside every cluster, ~0 if none)
     int *d_obs = nullptr;
-    long long *d_outc = nullptr;             // vds_outcomes_device: int64 [4][R_ext][C], made on the first request (in state_allocs)
-    int *d_heads = nullptr; int heads_L = 0; // vds_idle_heads_device: int32 [2][R_ext][C][heads_L], made on the first request (in state_allocs)
+    long long *d_outc = nullptr;             // vds_outcomes_device: int64 [4][R_ext][C], made on the first request (in MEM_STATE)
+    int *d_heads = nullptr; int heads_L = 0; // vds_idle_heads_device: int32 [2][R_ext][C][heads_L], made on the first request (in MEM_STATE)
     long long *d_cnt_per = nullptr, *d_cnt_tot = nullptr;
     int *d_actions = nullptr;
     size_t actions_cap = 0;
-    int *d_selftest = nullptr;
     bool profiling = false;
     // vds_run as one hipGraph: the launches of ticks [run_t0, run_t0 + run_n) captured once, replayed while nothing they
     // depend on (tables, capacities, stream) has changed
@@ -260,7 +234,6 @@ struct vds_handle {
                                              // per-slot forms, which leave the tables alone - a snapshot outlives them as it outlives a reset.)
     struct Snap {
         State D{};                           // the store: hdr, cnt, idle, ring, ring_min, ring_cnt, fl, inbox, sup, arr, out (the rest stays null)
-        std::vector<void *> allocs;
         long long bytes = 0;
         bool valid = false;
         unsigned gen = 0;                    // state_gen and the capacities the store was made for / the snapshot taken under
@@ -295,83 +268,35 @@ static int fail(vds_handle *h, int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail(h, VDS_EHIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
-// Guarded build (make canary, -DVDS_CANARY): every device table sits between two guard zones filled with a poison pattern
-// (GUARD_FRONT bytes before, GUARD_BACK after).  An out-of-bounds WRITE damages a guard - vds_debug_check_guards finds it at
-// the next check - and an out-of-bounds READ returns the poison (0xA5A5A5A5: a negative count / index), which the parity tests
-// then see as a wrong result or a fault at a far-away address, instead of whatever the neighbouring table happened to hold.
-#ifdef VDS_CANARY
-static const size_t GUARD_FRONT = 64u << 10, GUARD_BACK = 256u << 10;
-static const bool GUARDED = true;
-#else
-static const size_t GUARD_FRONT = 0, GUARD_BACK = 0;
-static const bool GUARDED = false;
-#endif
-struct GuardRec { void *base; size_t bytes; };
-static std::map<void *, GuardRec> g_guards;      // user pointer -> allocation (guarded build only; shared by all handles and threads:
-static std::mutex g_guards_mu;                   //  every access under this lock)
-
-static void dev_free(void *p) {
-    if (!p) return;
-    if (GUARDED) {
-        std::lock_guard<std::mutex> lk(g_guards_mu);
-        auto it = g_guards.find(p);
-        if (it != g_guards.end()) { (void)hipFree(it->second.base); g_guards.erase(it); return; }
-    }
-    (void)hipFree(p);
-}
-
-// dev_alloc / upload register their tables in `to` until the scope ends, then again where they did before
-struct AllocInto {
-    vds_handle *h; std::vector<void *> *old;
-    AllocInto(vds_handle *h_, std::vector<void *> *to) : h(h_), old(h_->alloc_sink) { h->alloc_sink = to; }
-    AllocInto(const AllocInto &) = delete;
-    ~AllocInto() { h->alloc_sink = old; }
-};
-
+// n elements (0: one) as a block of group g
 template <typename T>
-static int dev_alloc(vds_handle *h, T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    const size_t bytes = n * sizeof(T);
-    if (!GUARDED && h->alloc_sink == &h->order_allocs) {
-        // best fit among the cached blocks: large enough, at most 1.5 x + 64 KB of what is asked for
-        int best = -1;
-        for (int i = 0; i < (int)h->order_cache.size(); ++i) {
-            const size_t cb = h->order_cache[i].second;
-            if (cb >= bytes && cb <= bytes + bytes / 2 + 65536 && (best < 0 || cb < h->order_cache[best].second)) best = i;
-        }
-        if (best >= 0) {
-            *p = reinterpret_cast<T *>(h->order_cache[best].first);
-            h->order_bytes[(void *)*p] = h->order_cache[best].second;
-            h->order_cache.erase(h->order_cache.begin() + best);
-            h->order_allocs.push_back((void *)*p);
-            VDS_DIRTY_DEV((void *)*p, h->order_bytes[(void *)*p]);
-            return VDS_OK;
-        }
-    }
-    char *base = nullptr;
-    hipError_t e = hipMalloc((void **)&base, bytes + GUARD_FRONT + GUARD_BACK);
-    if (e != hipSuccess) return fail(h, VDS_ENOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-    if (GUARDED) {
-        (void)hipMemset(base, 0xA5, GUARD_FRONT);
-        (void)hipMemset(base + GUARD_FRONT + bytes, 0xA5, GUARD_BACK);
-        std::lock_guard<std::mutex> lk(g_guards_mu);
-        g_guards[(void *)(base + GUARD_FRONT)] = GuardRec{(void *)base, bytes};
-    }
-    *p = reinterpret_cast<T *>(base + GUARD_FRONT);
-    VDS_DIRTY_DEV((void *)*p, bytes);
-    (h->alloc_sink ? *h->alloc_sink : h->dev_allocs).push_back((void *)*p);
-    if (!GUARDED && h->alloc_sink == &h->order_allocs) h->order_bytes[(void *)*p] = bytes;
+static int dev_alloc(vds_handle *h, DevGroup &g, T **p, size_t n) {
+    const hipError_t e = g.alloc(p, n);
+    if (e != hipSuccess) return fail(h, VDS_ENOMEM, "device allocation of %zu bytes failed: %s", std::max<size_t>(n, 1) * sizeof(T), hipGetErrorString(e));
     return VDS_OK;
 }
+template <typename T>
+static int dev_alloc(vds_handle *h, Mem g, T **p, size_t n) { return dev_alloc(h, h->mem[g], p, n); }
 
 template <typename T, typename A>
-static int upload(vds_handle *h, T **p, const std::vector<T, A> &v) {
-    int rc = dev_alloc(h, p, v.size());
+static int upload(vds_handle *h, Mem g, T **p, const std::vector<T, A> &v) {
+    int rc = dev_alloc(h, g, p, v.size());
     if (rc) return rc;
     if (!v.empty()) HIPCHK(h, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return VDS_OK;
 }
+
+// What a change makes stale.  DAY_GRAPHS / GRAPH_TABLES: the day graphs hold other launches / the tables or capacities they read changed
+// (run_stale and tables_gen, which the hooked day graph and the reset image compare); STATE_MEANING: the state / result tables were re-made
+// or mean something else (state_gen: a snapshot taken before is void).  The first two move the same fields today, on purpose: the call
+// site records which of the two happened, nothing tells them apart yet.
+enum Changed : unsigned { DAY_GRAPHS = 1, GRAPH_TABLES = 2, STATE_MEANING = 4 };
+static void invalidate(vds_handle *h, unsigned changed) {
+    if (changed & (DAY_GRAPHS | GRAPH_TABLES)) { h->run_stale = true; h->tables_gen++; }
+    if (changed & STATE_MEANING) h->state_gen++;
+}
+// the episode clock back to the start of the day
+static void clock_reset(vds_handle *h) { h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1; }
 
 // No C++ exception may cross the C ABI (vds.h: "never abort"): host allocation failures and the like become a
 // status code + vds_last_error.
@@ -512,10 +437,8 @@ struct Chain {
 static int dev_copy_sync(vds_handle *h) {
     if (!h->S.dense) return VDS_OK;
     if (!h->d_S) {
-        HIPCHK(h, hipMalloc((void **)&h->d_S, sizeof(Static)));
-        HIPCHK(h, hipMalloc((void **)&h->d_D, sizeof(State)));
-        VDS_DIRTY_DEV(h->d_S, sizeof(Static));
-        VDS_DIRTY_DEV(h->d_D, sizeof(State));
+        int rc;
+        if ((rc = dev_alloc(h, MEM_STATIC, &h->d_S, 1)) || (rc = dev_alloc(h, MEM_STATIC, &h->d_D, 1))) { h->mem[MEM_STATIC].release(h->d_S); h->d_S = nullptr; return rc; }
     }
     h->S.self_dev = h->d_S; h->S.state_dev = h->d_D;
     Static want = h->S;
@@ -674,14 +597,7 @@ int vds_destroy(vds_handle *h) {
     if (!h) return VDS_OK;
     (void)hipSetDevice(h->cfg.device);
     (void)hipStreamSynchronize(h->stream);
-    for (void *p : h->dev_allocs) dev_free(p);
-    for (void *p : h->order_allocs) dev_free(p);
-    for (auto &b : h->order_cache) dev_free(b.first);
-    for (void *p : h->map_allocs) dev_free(p);
-    for (void *p : h->result_allocs) dev_free(p);
-    for (void *p : h->state_allocs) dev_free(p);
-    for (void *p : h->idle_allocs) dev_free(p);
-    for (void *p : h->snap.allocs) dev_free(p);
+    for (DevGroup &g : h->mem) g.clear();
     for (int i = 0; i < 2; ++i) {
         if (h->snap.pin_map[i]) (void)hipHostFree(h->snap.pin_map[i]);
         if (h->snap.pin_ev[i]) (void)hipEventDestroy(h->snap.pin_ev[i]);
@@ -691,8 +607,6 @@ int vds_destroy(vds_handle *h) {
     if (h->forms.ev) (void)hipEventDestroy(h->forms.ev);
     if (h->forms.pin_slow) (void)hipHostFree(h->forms.pin_slow);
     if (h->forms.pin_tick) (void)hipHostFree(h->forms.pin_tick);
-    if (h->d_S) (void)hipFree(h->d_S);
-    if (h->d_D) (void)hipFree(h->d_D);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
     return VDS_OK;
@@ -770,30 +684,30 @@ static int load_static_impl(vds_handle *h, const int32_t *cost, int32_t N, const
     long long *dl;
     unsigned char *d8;
     int4 *d4;
-    if ((rc = upload(h, &d, T.costp))) return rc; S.cost = d;
-    if ((rc = upload(h, &d, T.node2cluster))) return rc; S.node2cluster = d;
-    if ((rc = upload(h, &d, T.node_local))) return rc; S.node_local = d;
-    if ((rc = upload(h, &d, T.cl_off))) return rc; S.cl_off = d;
-    if ((rc = upload(h, &d, T.cl_nodes))) return rc; S.cl_nodes = d;
-    if ((rc = upload(h, &dl, T.blk_off))) return rc; S.blk_off = dl;
-    if ((rc = upload(h, &d, T.blk))) return rc; S.blk = d;
-    if ((rc = upload(h, &d, T.corder))) return rc; S.corder = d;
-    if ((rc = upload(h, &d8, T.blk8))) return rc; S.blk8 = d8;
-    if ((rc = upload(h, &d4, T.cdesc))) return rc; S.cdesc = d4;
+    if ((rc = upload(h, MEM_STATIC, &d, T.costp))) return rc; S.cost = d;
+    if ((rc = upload(h, MEM_STATIC, &d, T.node2cluster))) return rc; S.node2cluster = d;
+    if ((rc = upload(h, MEM_STATIC, &d, T.node_local))) return rc; S.node_local = d;
+    if ((rc = upload(h, MEM_STATIC, &d, T.cl_off))) return rc; S.cl_off = d;
+    if ((rc = upload(h, MEM_STATIC, &d, T.cl_nodes))) return rc; S.cl_nodes = d;
+    if ((rc = upload(h, MEM_STATIC, &dl, T.blk_off))) return rc; S.blk_off = dl;
+    if ((rc = upload(h, MEM_STATIC, &d, T.blk))) return rc; S.blk = d;
+    if ((rc = upload(h, MEM_STATIC, &d, T.corder))) return rc; S.corder = d;
+    if ((rc = upload(h, MEM_STATIC, &d8, T.blk8))) return rc; S.blk8 = d8;
+    if ((rc = upload(h, MEM_STATIC, &d4, T.cdesc))) return rc; S.cdesc = d4;
     S.cost8 = nullptr; S.lbc = nullptr;
-    if (T.u8_ok) { if ((rc = upload(h, &d8, T.cost8))) return rc; S.cost8 = d8; }
-    if (!T.lbc.empty()) { if ((rc = upload(h, &d8, T.lbc))) return rc; S.lbc = d8; }
-    if ((rc = upload(h, &d4, T.cdesc_ord))) return rc; S.cdesc_ord = d4;
+    if (T.u8_ok) { if ((rc = upload(h, MEM_STATIC, &d8, T.cost8))) return rc; S.cost8 = d8; }
+    if (!T.lbc.empty()) { if ((rc = upload(h, MEM_STATIC, &d8, T.lbc))) return rc; S.lbc = d8; }
+    if ((rc = upload(h, MEM_STATIC, &d4, T.cdesc_ord))) return rc; S.cdesc_ord = d4;
     S.blk8s = nullptr; S.blk32s = nullptr; S.cdesc_dense = nullptr;
     if (T.dense_ok) {
-        if ((rc = upload(h, &d8, T.blk_dense))) return rc;
+        if ((rc = upload(h, MEM_STATIC, &d8, T.blk_dense))) return rc;
         if (T.dense_bytes) S.blk8s = d8; else S.blk32s = reinterpret_cast<const int *>(d8);
-        if ((rc = upload(h, &d4, T.cdesc_dense))) return rc; S.cdesc_dense = d4;
+        if ((rc = upload(h, MEM_STATIC, &d4, T.cdesc_dense))) return rc; S.cdesc_dense = d4;
     }
     h->dense_static_ok = T.dense_ok;
-    if ((rc = upload(h, &d, T.dfs_off))) return rc; S.dfs_off = d;
-    if ((rc = upload(h, &d, T.dfs_seq))) return rc; S.dfs_seq = d;
-    { unsigned *dv; if ((rc = upload(h, &dv, T.vis_bits))) return rc; S.vis_bits = dv; }
+    if ((rc = upload(h, MEM_STATIC, &d, T.dfs_off))) return rc; S.dfs_off = d;
+    if ((rc = upload(h, MEM_STATIC, &d, T.dfs_seq))) return rc; S.dfs_seq = d;
+    { unsigned *dv; if ((rc = upload(h, MEM_STATIC, &dv, T.vis_bits))) return rc; S.vis_bits = dv; }
     // host mirrors (the blocks and byte copies are not kept)
     h->node2cluster.swap(T.node2cluster); h->node_local.swap(T.node_local); h->cl_off.swap(T.cl_off); h->cl_nodes.swap(T.cl_nodes);
     h->cost_host.swap(T.cost); h->corder_host.swap(T.corder); h->cdesc_dense_host.swap(T.cdesc_dense); h->cl_cmax.swap(T.cl_cmax);
@@ -829,6 +743,16 @@ static int slow_tick_slots(const vds_handle *h) {
     return tcap;
 }
 
+// the idle table lives in a group of its own: alloc_state makes it, vds_reset / vds_set_idle_cap may replace it alone
+static int alloc_idle(vds_handle *h, int idle_cap) {
+    const size_t B = (size_t)h->S.C * h->S.R;
+    h->mem[MEM_IDLE].release_all();
+    int rc = dev_alloc(h, MEM_IDLE, &h->D.idle, h->S.dense ? (B * idle_cap + 1) / 2 : B * idle_cap);      // (dense layout: 4-byte entries)
+    h->D.stamp = nullptr;
+    if (!rc && h->S.dense_st) rc = dev_alloc(h, MEM_IDLE, &h->D.stamp, B * idle_cap);                      // (stamp form: one u16 per idle entry)
+    return rc;
+}
+
 static int alloc_state(vds_handle *h, int O) {
     Static &S = h->S;
     State &D = h->D;
@@ -848,11 +772,10 @@ static int alloc_state(vds_handle *h, int O) {
     if (ring_cap > 65520) return fail(h, VDS_EINVAL, "ring_cap=%d > 65520 unsupported", ring_cap);
     int far_cap = h->cfg.far_cap > 0 ? round_up(h->cfg.far_cap, 64) : std::min(round_up(std::max(V, 1), 64), 256);
     if (S.dense && H > 32) { S.dense = 0; S.pull = 0; }  // (load_days_impl already decided this; kept as a guard: never a dense flag without its tables)
-    if (!h->state_allocs.empty() && S.idle_cap >= idle_cap && S.fl_cap == far_cap && S.H == H && S.ring_cap >= ring_cap && h->alloc_dense == S.dense && h->alloc_st == S.dense_st && h->alloc_R == R &&
+    if (!h->mem[MEM_STATE].empty() && S.idle_cap >= idle_cap && S.fl_cap == far_cap && S.H == H && S.ring_cap >= ring_cap && h->alloc_dense == S.dense && h->alloc_st == S.dense_st && h->alloc_R == R &&
         h->slow_tick_cap >= slow_tick_slots(h) && h->slow_tick_C == C)
         return VDS_OK;                                   // another day on the same handle: the state tables still fit
-    for (void *p : h->state_allocs) dev_free(p);
-    h->state_allocs.clear();
+    h->mem[MEM_STATE].release_all();
     h->d_outc = nullptr;                                 // (the outcome block lived there: made again on the next request)
     h->d_heads = nullptr; h->heads_L = 0;                // (and the idle-heads block)
     S.idle_cap = idle_cap; S.fl_cap = far_cap; S.in_cap = far_cap; S.H = H; S.ring_cap = ring_cap;
@@ -861,45 +784,34 @@ static int alloc_state(vds_handle *h, int O) {
     h->alloc_R = R;
     h->nodes_valid = false;                              // (d_veh_node is re-allocated below)
     int rc;
-    AllocInto into(h, &h->state_allocs);
-    if ((rc = dev_alloc(h, &D.hdr, B * HDR_WORDS))) return rc;
-    if ((rc = dev_alloc(h, &D.cnt, B * CNT_WORDS))) return rc;
-    {   // the idle table lives in its own allocation list: vds_reset / vds_set_idle_cap may replace it alone
-        std::vector<void *> *keep = h->alloc_sink;
-        h->alloc_sink = &h->idle_allocs;
-        for (void *p : h->idle_allocs) dev_free(p);
-        h->idle_allocs.clear();
-        rc = dev_alloc(h, &D.idle, S.dense ? (B * idle_cap + 1) / 2 : B * idle_cap);      // (dense layout: 4-byte entries)
-        D.stamp = nullptr;
-        if (!rc && S.dense_st) rc = dev_alloc(h, &D.stamp, B * idle_cap);                 // (stamp form: one u16 per idle entry)
-        h->alloc_sink = keep;
-        if (rc) return rc;
-    }
+    if ((rc = dev_alloc(h, MEM_STATE, &D.hdr, B * HDR_WORDS))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &D.cnt, B * CNT_WORDS))) return rc;
+    if ((rc = alloc_idle(h, idle_cap))) return rc;
     D.slow_tick = nullptr; D.slow_T = 0;
     {   // (one row per slot of the LONGEST resident day: another replica -> day map may lengthen the batch's day without coming back here)
         const int tcap = slow_tick_slots(h);
         h->slow_tick_cap = tcap; h->slow_tick_C = C;
-        if (S.dense && (rc = dev_alloc(h, &D.slow_tick, (size_t)tcap * C))) return rc;
+        if (S.dense && (rc = dev_alloc(h, MEM_STATE, &D.slow_tick, (size_t)tcap * C))) return rc;
         if (S.dense) D.slow_T = tcap;
     }
     D.dry = nullptr;
-    if (S.dense_st && (rc = dev_alloc(h, &D.dry, (size_t)R))) return rc;
+    if (S.dense_st && (rc = dev_alloc(h, MEM_STATE, &D.dry, (size_t)R))) return rc;
     D.sup = nullptr; D.sup_slot = nullptr;           // SupplyExpect kept in place (dense layout): planes by arrival slot + the current plane's index
     if (getenv("VDS_SUPPLY_INPLACE") && getenv("VDS_SUPPLY_INPLACE")[0] == '1') h->want_sup = true;
-    if (S.dense && h->want_sup && ((rc = dev_alloc(h, &D.sup, (size_t)VDS_SUP_PLANES * B)) || (rc = dev_alloc(h, &D.sup_slot, (size_t)1)))) return rc;
-    if ((rc = dev_alloc(h, &D.ring, S.dense ? ((size_t)H * B * ring_cap + 1) / 2 : (size_t)H * B * ring_cap))) return rc;      // (dense: 8-byte entries)
+    if (S.dense && h->want_sup && ((rc = dev_alloc(h, MEM_STATE, &D.sup, (size_t)VDS_SUP_PLANES * B)) || (rc = dev_alloc(h, MEM_STATE, &D.sup_slot, (size_t)1)))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &D.ring, S.dense ? ((size_t)H * B * ring_cap + 1) / 2 : (size_t)H * B * ring_cap))) return rc;      // (dense: 8-byte entries)
     D.ring_min = nullptr;
-    if (S.dense && (rc = dev_alloc(h, &D.ring_min, (size_t)H * B * ring_cap))) return rc;
+    if (S.dense && (rc = dev_alloc(h, MEM_STATE, &D.ring_min, (size_t)H * B * ring_cap))) return rc;
     S.ring_min_on = D.ring_min != nullptr;
-    if ((rc = dev_alloc(h, &D.ring_cnt, (size_t)H * B))) return rc;
-    if ((rc = dev_alloc(h, &D.fl, B * far_cap))) return rc;
-    if ((rc = dev_alloc(h, &D.inbox, 2 * B * far_cap))) return rc;
-    if ((rc = dev_alloc(h, &D.err, 16))) return rc;      // [0] sticky error bits, [2] buckets off the fast path, [4..15] instrumented build: why
-    if ((rc = dev_alloc(h, &D.work, 2 + 2 * B))) return rc;
-    if ((rc = dev_alloc(h, &h->d_veh_node, (size_t)R * V))) return rc;
-    if ((rc = dev_alloc(h, &h->d_obs, 5 * (size_t)R * C))) return rc;
-    if ((rc = dev_alloc(h, &h->d_cnt_per, (size_t)R * CNT_WORDS))) return rc;
-    if ((rc = dev_alloc(h, &h->d_cnt_tot, CNT_WORDS))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &D.ring_cnt, (size_t)H * B))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &D.fl, B * far_cap))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &D.inbox, 2 * B * far_cap))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &D.err, 16))) return rc;      // [0] sticky error bits, [2] buckets off the fast path, [4..15] instrumented build: why
+    if ((rc = dev_alloc(h, MEM_STATE, &D.work, 2 + 2 * B))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &h->d_veh_node, (size_t)R * V))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &h->d_obs, 5 * (size_t)R * C))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &h->d_cnt_per, (size_t)R * CNT_WORDS))) return rc;
+    if ((rc = dev_alloc(h, MEM_STATE, &h->d_cnt_tot, CNT_WORDS))) return rc;
     HIPCHK(h, hipMemset(D.err, 0, 16 * sizeof(int)));
     HIPCHK(h, hipMemset(D.work, 0, 2 * sizeof(int)));
     return VDS_OK;
@@ -919,29 +831,27 @@ static int apply_replica_map(vds_handle *h) {
     // the day groups' granule: aligned groups of 16 replicas on one day - or, on the dense layout at 16 lanes per replica (what order
     // days per replica run with), of 8: k_tick_dense then runs 8-row workgroups
     const bool gran8_ok = S.dense && S.dense_lpr == 16 && h->cfg.force_generic == 0 && !(getenv("VDS_ROW_GRAN8") && getenv("VDS_ROW_GRAN8")[0] == '0');
-    ReplicaPlan P = plan_replicas(h->replica_day.data(), RX, n_days, gran8_ok, h->cfg.force_generic == 0, h->state_allocs.empty() ? 0 : h->alloc_R);
+    ReplicaPlan P = plan_replicas(h->replica_day.data(), RX, n_days, gran8_ok, h->cfg.force_generic == 0, h->mem[MEM_STATE].empty() ? 0 : h->alloc_R);
     S.R = P.R; S.row_gran = P.row_gran; S.chunk_days = P.chunk_days;
     h->int2ext.swap(P.int2ext); h->ext2int.swap(P.ext2int);
     const std::vector<int> &rperm = P.rperm, &day_of_internal = P.day_of_internal;
-    for (void *p : h->map_allocs) dev_free(p);
-    h->map_allocs.clear();
-    AllocInto into(h, &h->map_allocs);
+    h->mem[MEM_MAP].release_all();
     int rc;
     int *d;
     S.rperm = nullptr; S.rslots = 0; S.int2ext = nullptr;
-    if (!rperm.empty()) { if ((rc = upload(h, &d, rperm))) return rc; S.rperm = d; S.rslots = (int)rperm.size(); }
-    if ((rc = upload(h, &d, day_of_internal))) return rc; S.replica_day = d;
-    if (!h->int2ext.empty()) { if ((rc = upload(h, &d, h->int2ext))) return rc; S.int2ext = d; }
+    if (!rperm.empty()) { if ((rc = upload(h, MEM_MAP, &d, rperm))) return rc; S.rperm = d; S.rslots = (int)rperm.size(); }
+    if ((rc = upload(h, MEM_MAP, &d, day_of_internal))) return rc; S.replica_day = d;
+    if (!h->int2ext.empty()) { if ((rc = upload(h, MEM_MAP, &d, h->int2ext))) return rc; S.int2ext = d; }
     {
         std::vector<int4> rdesc(S.R);
         for (int r = 0; r < S.R; ++r) { const DayDesc &dd = ddesc[day_of_internal[r]]; rdesc[r] = make_int4(dd.bkt_base, dd.now0, dd.T, dd.q_base); }
-        int4 *dr; if ((rc = upload(h, &dr, rdesc))) return rc; S.replica_desc = dr;
+        int4 *dr; if ((rc = upload(h, MEM_MAP, &dr, rdesc))) return rc; S.replica_desc = dr;
     }
     S.replica_desc2 = nullptr;
     if (S.pull) {
         std::vector<int4> rd2(S.R);
         for (int r = 0; r < S.R; ++r) rd2[r] = day_of_internal[r] < n_days ? h->pull_desc[day_of_internal[r]] : make_int4(0, 0, 0, 0);
-        int4 *d4r; if ((rc = upload(h, &d4r, rd2))) return rc; S.replica_desc2 = d4r;
+        int4 *d4r; if ((rc = upload(h, MEM_MAP, &d4r, rd2))) return rc; S.replica_desc2 = d4r;
     }
     return VDS_OK;
 }
@@ -960,14 +870,12 @@ static int alloc_results(vds_handle *h) {
     // that once held a very large day does not keep its peak footprint)
     auto fits = [](size_t need, size_t cap) { return need <= cap && (need == 0 ? cap == 0 : cap <= 4 * need + (1u << 20)); };
     if (h->D.out != nullptr && fits(need_out, h->res_cap_out) && fits(need_arr, h->res_cap_arr) && fits(need_slog, h->res_cap_slog)) return VDS_OK;
-    for (void *p : h->result_allocs) dev_free(p);
-    h->result_allocs.clear();
+    h->mem[MEM_RESULTS].release_all();
     h->D.out = nullptr; h->D.arr = nullptr; h->D.slog = nullptr;
     h->res_cap_out = h->res_cap_arr = h->res_cap_slog = 0;
-    AllocInto into(h, &h->result_allocs);
-    int rc = dev_alloc(h, &h->D.out, need_out);
-    if (!rc && need_arr) rc = dev_alloc(h, &h->D.arr, need_arr);
-    if (!rc && need_slog) rc = dev_alloc(h, &h->D.slog, need_slog);
+    int rc = dev_alloc(h, MEM_RESULTS, &h->D.out, need_out);
+    if (!rc && need_arr) rc = dev_alloc(h, MEM_RESULTS, &h->D.arr, need_arr);
+    if (!rc && need_slog) rc = dev_alloc(h, MEM_RESULTS, &h->D.slog, need_slog);
     if (!rc) { h->res_cap_out = need_out; h->res_cap_arr = need_arr; h->res_cap_slog = need_slog; }
     return rc;
 }
@@ -991,9 +899,9 @@ static int set_replica_days_impl(vds_handle *h, const int32_t *replica_day) {
         if ((rc = alloc_state(h, h->alloc_O))) return rc;
         if ((rc = alloc_results(h))) return rc;
     }
-    { h->run_stale = true; h->tables_gen++; h->state_gen++; }
+    invalidate(h, GRAPH_TABLES | STATE_MEANING);
     h->have_reset = false;                              // the episode state belongs to the previous map: vds_reset* must follow
-    h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1;
+    clock_reset(h);
     return VDS_OK;
 }
 
@@ -1009,15 +917,10 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
         // another day on the same handle (Reload, :130-212): the previous day's tables go, the static tables stay,
         // the state tables stay while their capacities still fit; vds_reset must follow
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (void *p : h->order_allocs) {
-            auto it = h->order_bytes.find(p);
-            if (!GUARDED && it != h->order_bytes.end()) { h->order_cache.emplace_back(p, it->second); h->order_bytes.erase(it); }
-            else dev_free(p);
-        }
-        h->order_allocs.clear();
-        { h->run_stale = true; h->tables_gen++; h->state_gen++; }
+        h->mem[MEM_ORDERS].park();
+        invalidate(h, GRAPH_TABLES | STATE_MEANING);
         h->have_orders = false; h->have_reset = false;
-        h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1;
+        clock_reset(h);
         h->err.clear();
     }
     lt.lap("sync + free the previous day");
@@ -1050,13 +953,12 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
     S.max_tick_orders = mto;
     int *d;
     int4 *d4;
-    std::optional<AllocInto> into(std::in_place, h, &h->order_allocs);
-    if ((rc = upload(h, &d4, so_rec))) return rc; S.so_rec = d4;
-    if ((rc = upload(h, &d, ot.bkt_off))) return rc; S.bkt_off = d;
-    if ((rc = upload(h, &d, ot.tick_off))) return rc; S.tick_off = d;
-    if ((rc = upload(h, &d, ot.so_pnode))) return rc; S.so_pnode = d;
-    if ((rc = upload(h, &d, ot.ord_q))) return rc; S.ord_q = d;
-    if ((rc = upload(h, &d, build_order_ranks(ot, nt)))) return rc; S.so_rank = d;
+    if ((rc = upload(h, MEM_ORDERS, &d4, so_rec))) return rc; S.so_rec = d4;
+    if ((rc = upload(h, MEM_ORDERS, &d, ot.bkt_off))) return rc; S.bkt_off = d;
+    if ((rc = upload(h, MEM_ORDERS, &d, ot.tick_off))) return rc; S.tick_off = d;
+    if ((rc = upload(h, MEM_ORDERS, &d, ot.so_pnode))) return rc; S.so_pnode = d;
+    if ((rc = upload(h, MEM_ORDERS, &d, ot.ord_q))) return rc; S.ord_q = d;
+    if ((rc = upload(h, MEM_ORDERS, &d, build_order_ranks(ot, nt)))) return rc; S.so_rank = d;
     lt.lap("upload records, ranks");
     S.so_lb = nullptr; S.so_vis = nullptr;
     if (h->dfs_mode && h->cfg.force_generic == 0 && h->max_seq <= 256 && mto < 65535 && (long long)so_rec.size() * S.seq_pad * 5 <= (6ll << 30)) {
@@ -1064,17 +966,17 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
         // of the same slot with a smaller id << 16) and, with byte costs, the cost bounds of those clusters (Static.lbc gathered
         // through the sequence once) - built ON THE DEVICE from the tables uploaded above (k_build_vis, vds_dfs.hip)
         int *d_b0;
-        if ((rc = upload(h, &d_b0, build_first_buckets(ot, nt)))) return rc;
+        if ((rc = upload(h, MEM_ORDERS, &d_b0, build_first_buckets(ot, nt)))) return rc;
         unsigned *dv;
-        if ((rc = dev_alloc(h, &dv, so_rec.size() * (size_t)S.seq_pad))) return rc;
+        if ((rc = dev_alloc(h, MEM_ORDERS, &dv, so_rec.size() * (size_t)S.seq_pad))) return rc;
         unsigned char *dl = nullptr;
-        if (!h->lbc_host.empty() && (rc = dev_alloc(h, &dl, so_rec.size() * (size_t)S.seq_pad))) return rc;
+        if (!h->lbc_host.empty() && (rc = dev_alloc(h, MEM_ORDERS, &dl, so_rec.size() * (size_t)S.seq_pad))) return rc;
         launch_build_vis(S, d_b0, dv, dl, (long long)so_rec.size(), h->stream);
         HIPCHK(h, hipGetLastError());
         S.so_vis = dv; S.so_lb = dl;
     }
     lt.lap("visit rows + bounds per order");
-    { DayDesc *dd; if ((rc = upload(h, &dd, ddesc))) return rc; S.day = dd; }
+    { DayDesc *dd; if ((rc = upload(h, MEM_ORDERS, &dd, ddesc))) return rc; S.day = dd; }
     // ---- dense layout (k_tick_dense: 4-byte idle entries, 8-byte arrival entries): the plain tick - one shared day, one day per
     //      workgroup chunk or one day per replica (day modes 0 / 1 / 2) -, ids that fit the packed keys.  vds_config.force_generic 5
     //      keeps the wide layout and k_tick_rows.
@@ -1134,9 +1036,9 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
         if (!pt.ok) S.pull = 0;
         else {
             S.pull_W = pt.W; S.pull_hmax = pt.hmax;
-            if ((rc = upload(h, &d, so_slot))) return rc; S.so_slot = d;
-            int2 *d2; if ((rc = upload(h, &d2, d_rec))) return rc; S.d_rec = d2;
-            if ((rc = upload(h, &d, pt.d_first))) return rc; S.d_first = d;
+            if ((rc = upload(h, MEM_ORDERS, &d, so_slot))) return rc; S.so_slot = d;
+            int2 *d2; if ((rc = upload(h, MEM_ORDERS, &d2, d_rec))) return rc; S.d_rec = d2;
+            if ((rc = upload(h, MEM_ORDERS, &d, pt.d_first))) return rc; S.d_first = d;
             h->pull_desc = pt.ddesc2;
             h->pull_drec = std::move(d_rec);          // (uploaded above; not read again below: a 25 MB copy at 16 days)
             build_slot_orders(ot, pt, nt, h->pull_slot_q);
@@ -1147,10 +1049,9 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
     // per-bucket descriptors of the dense tick with one shared day (Static.tdesc)
     S.tdesc = nullptr;
     if (S.dense && n_days == 1 && (int)h->corder_host.size() == C) {
-        int4 *dtd; if ((rc = upload(h, &dtd, build_bucket_descs(ot, h->corder_host, h->cdesc_dense_host, S.pull ? &pt : nullptr)))) return rc; S.tdesc = dtd;
+        int4 *dtd; if ((rc = upload(h, MEM_ORDERS, &dtd, build_bucket_descs(ot, h->corder_host, h->cdesc_dense_host, S.pull ? &pt : nullptr)))) return rc; S.tdesc = dtd;
     }
     lt.lap("bucket descriptors");
-    into.reset();                                       // (the order tables end here)
     if ((rc = apply_replica_map(h))) return rc;         // S.R (stored replicas), S.T, the map's arrays
     h->alloc_O = (int)std::min<long long>(ot.Ototal / n_days, 0x7fffffff);
     if ((rc = alloc_state(h, h->alloc_O))) return rc;
@@ -1179,15 +1080,10 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
     return VDS_OK;
 }
 
-static void drop_order_cache(vds_handle *h) {
-    for (auto &b : h->order_cache) dev_free(b.first);
-    h->order_cache.clear();
-}
-
 static int load_days_impl(vds_handle *h, int32_t n_days, const int64_t *day_off, const int32_t *release_min, const int32_t *pickup,
                           const int32_t *delivery, const int32_t *replica_day) {
     const int rc = load_days_body(h, n_days, day_off, release_min, pickup, delivery, replica_day);
-    drop_order_cache(h);         // blocks of the day before that this load did not take again
+    h->mem[MEM_ORDERS].drop_parked();         // blocks of the day before that this load did not take again
     return rc;
 }
 
@@ -1299,11 +1195,9 @@ static void compile_forms(vds_handle *h, int T) {
         bool ok = true;
         if (f.bmap_cap < f.bmap_host.size()) {
             (void)hipStreamSynchronize(h->stream);
-            if (f.d_bmap) { h->dev_allocs.erase(std::remove(h->dev_allocs.begin(), h->dev_allocs.end(), (void *)f.d_bmap), h->dev_allocs.end()); dev_free(f.d_bmap); }
+            h->mem[MEM_STATIC].release(f.d_bmap);
             f.d_bmap = nullptr; f.bmap_cap = 0;
-            std::vector<void *> *sink = h->alloc_sink; h->alloc_sink = nullptr;
-            ok = dev_alloc(h, &f.d_bmap, f.bmap_host.size()) == VDS_OK;
-            h->alloc_sink = sink;
+            ok = dev_alloc(h, MEM_STATIC, &f.d_bmap, f.bmap_host.size()) == VDS_OK;
             if (ok) f.bmap_cap = f.bmap_host.size();
         }
         ok = ok && hipMemcpyAsync(f.d_bmap, f.bmap_host.data(), f.bmap_host.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream) == hipSuccess;
@@ -1313,7 +1207,7 @@ static void compile_forms(vds_handle *h, int T) {
                 if (f.slot[t].kind == TickForms::MIXED) { f.slot[t].kind = TickForms::WIDE; std::fill_n(f.plane.begin() + (size_t)t * C, C, 1); }
         }
     }
-    h->run_stale = true; h->tables_gen++;           // the day graph holds other kernels
+    invalidate(h, DAY_GRAPHS);                      // the day graph holds other kernels
 }
 // the episode that ends here (h->t slots of it were run): its counters into pinned host memory, behind the stream (false: no pinned
 // memory)
@@ -1402,8 +1296,7 @@ static void adapt_dense(vds_handle *h) {
             const char *t256 = getenv("VDS_DENSE_TAB256");
             S.dense_lpr = 16; S.dense_tab = (t256 && *t256 == '0') ? 128 : 256;
             f.adapt = 1;
-            h->run_stale = true; h->tables_gen++;               // the day graph holds the other kernel
-            h->state_gen++;                                     // (and a snapshot belongs to the base form it was taken under)
+            invalidate(h, DAY_GRAPHS | STATE_MEANING);          // the day graph holds the other kernel, and a snapshot belongs to the base form it was taken under
             return;
         }
     }
@@ -1433,14 +1326,11 @@ static int reset_device(vds_handle *h) {
         if (h->reset_img_words < iw || h->reset_base_words < bw) {
             // (plain allocations owned by the handle: they outlive a re-load of the order tables)
             HIPCHK(h, hipStreamSynchronize(h->stream));
-            for (void *old : {(void *)h->d_reset_img, (void *)h->d_reset_base})
-                if (old) { h->dev_allocs.erase(std::remove(h->dev_allocs.begin(), h->dev_allocs.end(), old), h->dev_allocs.end()); dev_free(old); }
+            h->mem[MEM_STATIC].release(h->d_reset_img); h->mem[MEM_STATIC].release(h->d_reset_base);
             h->d_reset_img = nullptr; h->d_reset_base = nullptr;
             h->reset_img_words = h->reset_base_words = 0; h->img_valid = false;
-            std::vector<void *> *sink = h->alloc_sink; h->alloc_sink = nullptr;
-            int rc = dev_alloc(h, &h->d_reset_img, iw);
-            if (!rc) rc = dev_alloc(h, &h->d_reset_base, bw);
-            h->alloc_sink = sink;
+            int rc = dev_alloc(h, MEM_STATIC, &h->d_reset_img, iw);
+            if (!rc) rc = dev_alloc(h, MEM_STATIC, &h->d_reset_base, bw);
             if (rc) return rc;
             h->reset_img_words = iw; h->reset_base_words = bw;
         }
@@ -1455,7 +1345,7 @@ static int reset_device(vds_handle *h) {
         launch_reset(S, h->D, h->d_veh_node, h->stream);
     }
     HIPCHK(h, hipGetLastError());
-    h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1;
+    clock_reset(h);
     h->restored_episode = false;
     h->have_reset = true; h->nodes_valid = true;
     return VDS_OK;
@@ -1468,20 +1358,13 @@ static int set_idle_cap_impl(vds_handle *h, int32_t cap) {
     if (cap < 1) return fail(h, VDS_EINVAL, "vds_set_idle_cap: bad capacity %d", cap);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    { h->run_stale = true; h->tables_gen++; }
+    invalidate(h, GRAPH_TABLES);
     cap = std::min(round_up(cap, 64), round_up(std::max(h->S.V, 1), 64));
     if (cap > (1 << 24)) return fail(h, VDS_EINVAL, "vds_set_idle_cap: %d > 2^24 unsupported", cap);
     if (cap == h->S.idle_cap) return VDS_OK;
     if (h->S.dense_st && cap > 16384) return fail(h, VDS_ECAPACITY, "vds_set_idle_cap: neighbour search on the dense layout holds at most 16384 entries per list (VDS_DENSE_DFS=0 keeps the wide layout)");
-    h->state_gen++;                                     // (the idle tables are replaced: a snapshot of the old ones is void)
-    for (void *p : h->idle_allocs) dev_free(p);
-    h->idle_allocs.clear();
-    h->alloc_sink = &h->idle_allocs;
-    const size_t B0 = (size_t)h->S.C * h->S.R;
-    int rc = dev_alloc(h, &h->D.idle, h->S.dense ? (B0 * cap + 1) / 2 : B0 * cap);
-    h->D.stamp = nullptr;
-    if (!rc && h->S.dense_st) rc = dev_alloc(h, &h->D.stamp, B0 * cap);
-    h->alloc_sink = nullptr;
+    invalidate(h, STATE_MEANING);                       // (the idle tables are replaced: a snapshot of the old ones is void)
+    const int rc = alloc_idle(h, cap);
     if (rc) return rc;
     h->S.idle_cap = cap;
     h->idle_cap_grown = cap;
@@ -1494,9 +1377,9 @@ static int set_idle_cap_impl(vds_handle *h, int32_t cap) {
 // device scratch of vds_reset / vds_reset_random: staged start nodes, fullest start list per replica, first offending node
 static int ensure_reset_scratch(vds_handle *h) {
     int rc;
-    if (!h->d_veh_stage && (rc = dev_alloc(h, &h->d_veh_stage, std::max<size_t>((size_t)h->R_ext * h->S.V, 1)))) return rc;
-    if (!h->d_fullest && (rc = dev_alloc(h, &h->d_fullest, (size_t)h->R_ext))) return rc;
-    if (!h->d_bad && (rc = dev_alloc(h, &h->d_bad, (size_t)1))) return rc;
+    if (!h->d_veh_stage && (rc = dev_alloc(h, MEM_STATIC, &h->d_veh_stage, std::max<size_t>((size_t)h->R_ext * h->S.V, 1)))) return rc;
+    if (!h->d_fullest && (rc = dev_alloc(h, MEM_STATIC, &h->d_fullest, (size_t)h->R_ext))) return rc;
+    if (!h->d_bad && (rc = dev_alloc(h, MEM_STATIC, &h->d_bad, (size_t)1))) return rc;
     return VDS_OK;
 }
 
@@ -1575,7 +1458,7 @@ static int reset_random_impl(vds_handle *h, const uint64_t *seeds) {
     if ((size_t)(624 + S.C) * sizeof(int) > 64 * 1024) return fail(h, VDS_EINVAL, "vds_reset_random: %d clusters exceed the generator's LDS histogram", S.C);
     if (S.N < 1) return fail(h, VDS_EINVAL, "vds_reset_random: no nodes");
     int rc;
-    if (!h->d_seeds && (rc = dev_alloc(h, &h->d_seeds, (size_t)h->R_ext))) return rc;
+    if (!h->d_seeds && (rc = dev_alloc(h, MEM_STATIC, &h->d_seeds, (size_t)h->R_ext))) return rc;
     if ((rc = ensure_reset_scratch(h))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, (size_t)h->R_ext * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     // drawn into the staging array, like vds_reset's upload: the nodes of the previous reset stay in place until these have passed
@@ -1824,7 +1707,7 @@ int vds_get_run_groups(vds_handle *h) {
 int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger) {
     if (!h) return VDS_EINVAL;
     if (groups > RUN_GROUPS_MAX || stagger > 2) return fail(h, VDS_EINVAL, "vds_set_run_groups: groups <= %d, stagger 0 / 1 / 2 (or negative: default)", RUN_GROUPS_MAX);
-    { h->run_stale = true; h->tables_gen++; }
+    invalidate(h, DAY_GRAPHS);
     h->run_groups = groups > 0 ? groups : -1;
     return VDS_OK;
 }
@@ -1973,9 +1856,8 @@ int vds_sync(vds_handle *h) {
 // blocks (d_obs, d_outc, d_heads, d_cnt_*) and stamp (every stamp is 0xFFFF between API calls: the lists are compact there).
 static void snap_free(vds_handle *h) {
     vds_handle::Snap &s = h->snap;
-    if (!s.allocs.empty()) (void)hipStreamSynchronize(h->stream);           // (a copy may still be running)
-    for (void *p : s.allocs) dev_free(p);
-    s.allocs.clear();
+    if (!h->mem[MEM_SNAP].empty()) (void)hipStreamSynchronize(h->stream);           // (a copy may still be running)
+    h->mem[MEM_SNAP].release_all();
     for (int i = 0; i < 2; ++i) {
         if (s.pin_map[i]) (void)hipHostFree(s.pin_map[i]);
         if (s.pin_ev[i]) (void)hipEventDestroy(s.pin_ev[i]);
@@ -1987,7 +1869,7 @@ static void snap_free(vds_handle *h) {
 static bool snap_fits(const vds_handle *h) {
     const vds_handle::Snap &s = h->snap;
     const Static &S = h->S;
-    return !s.allocs.empty() && s.gen == h->state_gen && s.R == S.R && s.C == S.C && s.idle_cap == S.idle_cap && s.ring_cap == S.ring_cap && s.fl_cap == S.fl_cap &&
+    return !h->mem[MEM_SNAP].empty() && s.gen == h->state_gen && s.R == S.R && s.C == S.C && s.idle_cap == S.idle_cap && s.ring_cap == S.ring_cap && s.fl_cap == S.fl_cap &&
            s.H == S.H && s.dense == S.dense && s.Oq == S.Oq && s.arr_slots == S.arr_slots && s.sup == (h->D.sup != nullptr) && s.arr == (S.pull && h->D.arr != nullptr);
 }
 static int snap_alloc(vds_handle *h) {
@@ -1998,9 +1880,8 @@ static int snap_alloc(vds_handle *h) {
     const size_t B = (size_t)S.C * S.R, HB = (size_t)S.H * B;
     s.gen = h->state_gen; s.R = S.R; s.C = S.C; s.idle_cap = S.idle_cap; s.ring_cap = S.ring_cap; s.fl_cap = S.fl_cap; s.H = S.H; s.dense = S.dense;
     s.Oq = S.Oq; s.arr_slots = S.arr_slots; s.sup = D.sup != nullptr; s.arr = S.pull && D.arr != nullptr;
-    AllocInto into(h, &s.allocs);
     size_t bytes = 0;
-    auto get = [&](auto **p, size_t n) { const int rc = dev_alloc(h, p, n); if (!rc) bytes += std::max<size_t>(n, 1) * sizeof(**p); return rc; };
+    auto get = [&](auto **p, size_t n) { const int rc = dev_alloc(h, MEM_SNAP, p, n); if (!rc) bytes += std::max<size_t>(n, 1) * sizeof(**p); return rc; };
     int rc;
     // (sized like alloc_state / alloc_results size the tables they mirror)
     if ((rc = get(&s.D.hdr, B * HDR_WORDS)) || (rc = get(&s.D.cnt, B * CNT_WORDS)) ||
@@ -2183,7 +2064,7 @@ static int apply_dispatch_impl(vds_handle *h, int32_t n, const int32_t *replica,
     const size_t need = (size_t)7 * n + grp_off.size();
     if (need > h->actions_cap) {
         int *p;
-        int rc = dev_alloc(h, &p, need * 2);
+        int rc = dev_alloc(h, MEM_STATIC, &p, need * 2);
         if (rc) return rc;
         h->d_actions = p; h->actions_cap = need * 2;
     }
@@ -2269,13 +2150,12 @@ int vds_supply_inplace(vds_handle *h, void **ring, int64_t *stride_plane, int64_
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->want_sup = true;
         int rc;
-        AllocInto into(h, &h->state_allocs);
-        if ((rc = dev_alloc(h, &h->D.sup, (size_t)VDS_SUP_PLANES * h->S.C * h->S.R)) || (rc = dev_alloc(h, &h->D.sup_slot, (size_t)1))) { h->D.sup = nullptr; h->D.sup_slot = nullptr; return rc; }
+        if ((rc = dev_alloc(h, MEM_STATE, &h->D.sup, (size_t)VDS_SUP_PLANES * h->S.C * h->S.R)) || (rc = dev_alloc(h, MEM_STATE, &h->D.sup_slot, (size_t)1))) { h->D.sup = nullptr; h->D.sup_slot = nullptr; return rc; }
         HIPCHK(h, hipMemsetAsync(h->D.sup, 0, (size_t)VDS_SUP_PLANES * h->S.C * h->S.R * sizeof(int), h->stream));
         HIPCHK(h, hipMemsetAsync(h->D.sup_slot, 0, sizeof(int), h->stream));
-        { h->run_stale = true; h->tables_gen++; h->state_gen++; }
+        invalidate(h, GRAPH_TABLES | STATE_MEANING);
         h->have_reset = false;                      // vds_reset / vds_reset_again / vds_reset_random must follow
-        h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1;
+        clock_reset(h);
     }
     *ring = h->D.sup; *slot_word = h->D.sup_slot; *planes = VDS_SUP_PLANES;
     *stride_plane = (int64_t)h->S.C * h->S.R; *stride_cluster = h->S.R; *stride_replica = 1;
@@ -2295,9 +2175,8 @@ int vds_counters_device(vds_handle *h, void **dev_ptr) {
 // int64 [4][R_ext][C] block, made on the first request (it lives with the state tables: re-made when they are).
 static int ensure_outcomes(vds_handle *h) {
     if (h->d_outc) return VDS_OK;
-    AllocInto into(h, &h->state_allocs);
     const size_t n = 4 * (size_t)h->R_ext * h->S.C;
-    const int rc = dev_alloc(h, &h->d_outc, n);
+    const int rc = dev_alloc(h, MEM_STATE, &h->d_outc, n);
     if (rc) { h->d_outc = nullptr; return rc; }
     HIPCHK(h, hipMemsetAsync(h->d_outc, 0, n * sizeof(long long), h->stream));
     return VDS_OK;
@@ -2340,14 +2219,11 @@ static int ensure_idle_heads(vds_handle *h, int L) {
     if (h->d_heads && h->heads_L == L) return VDS_OK;
     if (h->d_heads) {                                    // another L: the block is made again (work that reads the old one may be in flight)
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        auto &v = h->state_allocs;
-        v.erase(std::remove(v.begin(), v.end(), (void *)h->d_heads), v.end());
-        dev_free(h->d_heads);
+        h->mem[MEM_STATE].release(h->d_heads);
         h->d_heads = nullptr; h->heads_L = 0;
     }
-    AllocInto into(h, &h->state_allocs);
     const size_t n = 2 * (size_t)h->R_ext * h->S.C * L;
-    const int rc = dev_alloc(h, &h->d_heads, n);
+    const int rc = dev_alloc(h, MEM_STATE, &h->d_heads, n);
     if (rc) { h->d_heads = nullptr; return rc; }
     h->heads_L = L;
     HIPCHK(h, hipMemsetAsync(h->d_heads, 0xFF, n * sizeof(int), h->stream));      // (-1: empty lists until the first refresh)
@@ -2683,6 +2559,13 @@ int vds_debug_check_guards(vds_handle *h) {
     return bad;
 }
 
+// device blocks of this process that are live (parked ones included) and their bytes, as dev_raw_alloc / dev_free count them
+int vds_debug_device_blocks(int64_t out[2]) {
+    if (!out) return VDS_EINVAL;
+    out[0] = g_dev_blocks.load(); out[1] = g_dev_bytes.load();
+    return VDS_OK;
+}
+
 // Guarded build only: damages one guard zone on purpose (one byte behind the header table), so that the test of the guard
 // check itself has something to find.  Other builds: VDS_EINVAL.
 int vds_debug_poke_guard(vds_handle *h) {
@@ -2701,15 +2584,10 @@ int vds_debug_dirty_probe(vds_handle *h, int32_t out[4]) {
 #ifdef VDS_DIRTY
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int *p = nullptr;
-    std::vector<void *> mine;
-    int rc;
-    {
-        AllocInto into(h, &mine);
-        rc = dev_alloc(h, &p, (size_t)4);
-    }
+    DevGroup mine;
+    const int rc = dev_alloc(h, mine, &p, (size_t)4);
     if (rc) return rc;
     const hipError_t e = hipMemcpy(out, p, 4 * sizeof(int), hipMemcpyDeviceToHost);
-    dev_free(p);
     if (e != hipSuccess) return fail(h, VDS_EHIP, "vds_debug_dirty_probe: copying the table back failed: %s", hipGetErrorString(e));
     return VDS_OK;
 #else
@@ -2754,11 +2632,10 @@ int vds_selftest_dpp(vds_handle *h, const int32_t *in, int32_t *out_wave, int32_
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t n = (size_t)nwaves * 64;
     int *din = nullptr, *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-    HIPCHK(h, hipMalloc((void **)&din, n * sizeof(int)));
-    HIPCHK(h, hipMalloc((void **)&d0, (size_t)nwaves * sizeof(int)));
-    HIPCHK(h, hipMalloc((void **)&d1, n * sizeof(int)));
-    HIPCHK(h, hipMalloc((void **)&d2, n * sizeof(int)));
-    HIPCHK(h, hipMalloc((void **)&d3, n * sizeof(int)));
+    DevGroup scratch;                                    // (freed on every way out)
+    int rc;
+    if ((rc = dev_alloc(h, scratch, &din, n)) || (rc = dev_alloc(h, scratch, &d0, (size_t)nwaves)) || (rc = dev_alloc(h, scratch, &d1, n)) ||
+        (rc = dev_alloc(h, scratch, &d2, n)) || (rc = dev_alloc(h, scratch, &d3, n))) return rc;
     HIPCHK(h, hipMemcpy(din, in, n * sizeof(int), hipMemcpyHostToDevice));
     launch_selftest_dpp(din, d0, d1, d2, d3, nwaves, h->stream);
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2766,7 +2643,6 @@ int vds_selftest_dpp(vds_handle *h, const int32_t *in, int32_t *out_wave, int32_
     HIPCHK(h, hipMemcpy(out_rowmin, d1, n * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(out_rowsum, d2, n * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(h, hipMemcpy(out_rowscan, d3, n * sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipFree(din); (void)hipFree(d0); (void)hipFree(d1); (void)hipFree(d2); (void)hipFree(d3);
     return VDS_OK;
 }
 
