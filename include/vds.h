@@ -356,6 +356,36 @@ int vds_read_idle_heads(vds_handle *h, int32_t L, int32_t *veh, int32_t *node);
  * launched.  L outside 0 .. VDS_IDLE_HEADS_MAX: VDS_EINVAL.  A parameter of its own, not a bit of `planes` (which stays 0 .. 63). */
 int vds_run_hooked_idle_heads(vds_handle *h, int32_t L);
 
+/* The per-vehicle state of every replica - the fields of `Vehicle` that the tick path changes (objects.py:75-89: LocationNode /
+ * Cluster, Orders, DeliveryPoint, the arrival time kept in Cluster.VehiclesArrivetime, simulator.py:954-960) - as six int32 planes
+ * [6][R][V], plane k at dev_ptr + k*R*V elements, replicas in the caller's order.  Planes 0 .. 4 mean exactly what the fields of
+ * vds_read_vehicles mean (state widened to int32), for every replica at once; `planes` is a mask of the VDS_VEH_* bits:
+ *   VDS_VEH_STATE   0 idle (in some Cluster.IdleVehicles), 1 on the way with an order, 2 on the way after a dispatch; -1 in
+ *                   neither container (cannot happen)
+ *   VDS_VEH_NODE    idle: LocationNode; on the way: DeliveryPoint - a global node id
+ *   VDS_VEH_CLUSTER the cluster whose IdleVehicles / VehiclesArrivetime holds the vehicle (on the way: the destination's cluster -
+ *                   the trip origin is not kept on the device, see vds_read_vehicles)
+ *   VDS_VEH_ARRIVE  arrival minute on the day clock, -1 when idle
+ *   VDS_VEH_ORDER   carried Order.ID, -1 when none
+ *   VDS_VEH_SOURCE  where the engine keeps the vehicle: 0 idle list, 1 static arrival slot, 2 arrival ring, 3 far list, 4 far
+ *                   inbox (no reference counterpart; diagnostic)
+ * vds_vehicles_device refreshes the requested planes asynchronously on the handle's stream from the state as it stands - after a
+ * reset, a step, the slot's dispatch calls, an advance, a vds_run*, a restore - and returns the block's device address.  Every
+ * element of a requested plane is written; a plane that is not requested keeps what the block held (as vds_obs_device_planes).
+ * A replica whose order day is over (vds_load_order_days) reports its standing state at its own last slot.  VDS_EINVAL before
+ * vds_reset and for `planes` outside 1 .. 63.  The block is made on the first call and fixed until the tables are re-made (as for
+ * vds_outcomes_device).  No tick, vds_run or vds_run_hooked computes it.
+ * vds_read_vehicles_all: refreshes the same planes, then copies the requested ones to the host (synchronous): out is
+ * [popcount(planes)][R][V], in ascending bit order. */
+#define VDS_VEH_STATE   1
+#define VDS_VEH_NODE    2
+#define VDS_VEH_CLUSTER 4
+#define VDS_VEH_ARRIVE  8
+#define VDS_VEH_ORDER  16
+#define VDS_VEH_SOURCE 32
+int vds_vehicles_device(vds_handle *h, int32_t planes, void **dev_ptr);
+int vds_read_vehicles_all(vds_handle *h, int32_t planes, int32_t *out);
+
 /* Snapshot and restore of the episode state, with per-replica forking (no reference counterpart: a Simulation cannot go back; the
  * nearest thing is Reload + replaying the day, simulator.py:130-212, :1048-1091).
  * vds_snapshot saves the episode state of every replica as it stands: the idle lists, the vehicles on their way (arrival ring, far
@@ -369,7 +399,7 @@ int vds_run_hooked_idle_heads(vds_handle *h, int32_t L);
  * one a vds_reset issues to regrow them), the first vds_supply_inplace, the whole-day change of k_tick_dense's base form.
  * vds_restore makes replica r (the caller's index) continue from the snapshot's replica src_replica[r] - [replicas] host values, not
  * retained; NULL: every replica from itself, the plain rollback.  Afterwards every read entry point (vds_read_obs and the device
- * planes, vds_read_counters, vds_read_orders, vds_read_lists, vds_read_vehicles, vds_read_outcomes, vds_read_idle_heads, vds_clock)
+ * planes, vds_read_counters, vds_read_orders, vds_read_lists, vds_read_vehicles, vds_read_vehicles_all, vds_read_outcomes, vds_read_idle_heads, vds_clock)
  * answers as it did at the snapshot with replica r showing src_replica[r]'s values, and vds_step / vds_run / vds_run_hooked continue
  * from the restored slot.  Asynchronous.  A snapshot can be restored any number of times.  VDS_ESTATE "no snapshot" when there is
  * none or it is void; VDS_EINVAL for a map entry outside [0, replicas); VDS_EINVAL with order days per replica when replica r and

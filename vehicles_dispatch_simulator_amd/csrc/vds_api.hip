@@ -97,7 +97,7 @@ enum Mem {
     MEM_ORDERS,                          // tables of the loaded day (parked by the next vds_load_orders* for its own tables, DevGroup::recycle)
     MEM_MAP,                             // the replica -> day map's device arrays (replaced by vds_set_replica_days / the next load)
     MEM_RESULTS,                         // per-replica result tables out / arr / slog (sized by S.R)
-    MEM_STATE,                           // per-replica state (kept across days while the capacities still fit), with d_outc and d_heads
+    MEM_STATE,                           // per-replica state (kept across days while the capacities still fit), with d_outc, d_heads and d_veh
     MEM_IDLE,                            // the idle table alone (regrown by vds_reset / vds_set_idle_cap)
     MEM_SNAP,                            // the snapshot store
     MEM_GROUPS
@@ -221,6 +221,7 @@ struct vds_handle {
     int hook_t0 = -1, hook_n = 0, hook_G = 1, hook_planes = 0, hook_K = 0;
     unsigned hook_gen = 0;
     const long long *hook_outc = nullptr;
+    int *d_veh = nullptr;                    // vds_vehicles_device: int32 [6][R_ext][V], made on the first request (in MEM_STATE)
     int hooked_heads_L = 0;                  // vds_run_hooked_idle_heads: > 0 - every slot of vds_run_hooked refreshes the heads block (sticky)
     const int *hook_heads = nullptr; int hook_heads_L = 0;   // ... and what the graph at hand was built with
     const void *hook_actions = nullptr;
@@ -778,6 +779,7 @@ static int alloc_state(vds_handle *h, int O) {
     h->mem[MEM_STATE].release_all();
     h->d_outc = nullptr;                                 // (the outcome block lived there: made again on the next request)
     h->d_heads = nullptr; h->heads_L = 0;                // (and the idle-heads block)
+    h->d_veh = nullptr;                                  // (and the per-vehicle planes)
     S.idle_cap = idle_cap; S.fl_cap = far_cap; S.in_cap = far_cap; S.H = H; S.ring_cap = ring_cap;
     const size_t B = (size_t)C * R;
     h->alloc_dense = S.dense; h->alloc_st = S.dense_st;
@@ -1853,7 +1855,7 @@ int vds_sync(vds_handle *h) {
 // replica map (vds_snapshot.hip).  What is saved: hdr, cnt, idle, ring, ring_min, ring_cnt, fl, both inbox parities, sup, arr, out and the
 // clock (t, last_stepped, the dispatch sequence numbers).  What is not: work / slog / dry (consumed or cleared inside the slot's own
 // launches), err / slow_tick / sup_slot (rewritten by every tick launch; the slot word is set to the restored slot's), the derived
-// blocks (d_obs, d_outc, d_heads, d_cnt_*) and stamp (every stamp is 0xFFFF between API calls: the lists are compact there).
+// blocks (d_obs, d_outc, d_heads, d_veh, d_cnt_*: not saved, refreshed on request after a restore) and stamp (every stamp is 0xFFFF between API calls: the lists are compact there).
 static void snap_free(vds_handle *h) {
     vds_handle::Snap &s = h->snap;
     if (!h->mem[MEM_SNAP].empty()) (void)hipStreamSynchronize(h->stream);           // (a copy may still be running)
@@ -2258,6 +2260,57 @@ static int read_idle_heads_impl(vds_handle *h, int32_t L, int32_t *veh, int32_t 
 
 int vds_read_idle_heads(vds_handle *h, int32_t L, int32_t *veh, int32_t *node) {
     return guarded(h, "vds_read_idle_heads", [&] { return read_idle_heads_impl(h, L, veh, node); });
+}
+
+// The fields of `Vehicle` that the tick path changes (objects.py:75-89) for every replica at once: k_vehicle_lists / k_vehicle_pull
+// (vds_vehicle_planes.hip) into the int32 [6][R_ext][V] block, made on the first request (it lives with the state tables: re-made
+// when they are).  read_lists_impl + read_vehicles_impl below are the specification of what the planes hold.
+static int ensure_vehicles(vds_handle *h) {
+    if (h->d_veh) return VDS_OK;
+    const size_t n = std::max<size_t>(6 * (size_t)h->R_ext * h->S.V, 1);
+    const int rc = dev_alloc(h, MEM_STATE, &h->d_veh, n);
+    if (rc) { h->d_veh = nullptr; return rc; }
+    HIPCHK(h, hipMemsetAsync(h->d_veh, 0xFF, n * sizeof(int), h->stream));        // (-1: "in neither container" until a plane's first refresh)
+    return VDS_OK;
+}
+
+static int vehicles_device_impl(vds_handle *h, int32_t planes, void **dev_ptr) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_vehicles_device: call vds_reset first");
+    if (planes < 1 || planes > 63) return fail(h, VDS_EINVAL, "vds_vehicles_device: planes = %d is outside 1 .. 63", planes);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int rc = ensure_vehicles(h);
+    if (rc) return rc;
+    const size_t RV = (size_t)h->R_ext * h->S.V;
+    // every element of a requested plane is written, whatever the tables hold: -1 first (runs of neighbouring planes in one call), then the scatter
+    for (int k = 0; k < 6 && RV > 0;) {
+        if (!(planes >> k & 1)) { ++k; continue; }
+        int e = k;
+        while (e < 6 && (planes >> e & 1)) ++e;
+        HIPCHK(h, hipMemsetAsync(h->d_veh + k * RV, 0xFF, (size_t)(e - k) * RV * sizeof(int), h->stream));
+        k = e;
+    }
+    if (RV > 0) launch_vehicle_planes(h->S, h->D, h->last_stepped, planes, h->d_veh, h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (dev_ptr) *dev_ptr = h->d_veh;
+    return VDS_OK;
+}
+
+int vds_vehicles_device(vds_handle *h, int32_t planes, void **dev_ptr) {
+    return guarded(h, "vds_vehicles_device", [&] { return vehicles_device_impl(h, planes, dev_ptr); });
+}
+
+static int read_vehicles_all_impl(vds_handle *h, int32_t planes, int32_t *out) {
+    if (h && h->have_reset && !out) return fail(h, VDS_EINVAL, "vds_read_vehicles_all: out is NULL");
+    const int rc = vehicles_device_impl(h, planes, nullptr);
+    if (rc) return rc;
+    const size_t RV = (size_t)h->R_ext * h->S.V;
+    for (int k = 0, n = 0; k < 6 && RV > 0; ++k)
+        if (planes >> k & 1) HIPCHK(h, hipMemcpyAsync(out + (size_t)n++ * RV, h->d_veh + k * RV, RV * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return vds_sync(h);
+}
+
+int vds_read_vehicles_all(vds_handle *h, int32_t planes, int32_t *out) {
+    return guarded(h, "vds_read_vehicles_all", [&] { return read_vehicles_all_impl(h, planes, out); });
 }
 
 int vds_run_hooked_idle_heads(vds_handle *h, int32_t L) {

@@ -15,6 +15,7 @@ from . import _lib
 PICKUP_REJECT_THRESHOLD = 600_000_000_000   # int(config/setting.py:7 PICKUPTIMEWINDOW), quirk Q3
 PLANE_OUTCOMES = 32                         # vds_run_hooked plane bit of the per-cluster order outcomes (VDS_PLANE_OUTCOMES)
 OUTCOME_NAMES = ("served", "rejected", "wait_sum", "value_sum")
+VEHICLE_PLANE_NAMES = ("state", "node", "cluster", "arrive_min", "order", "source")      # planes of vds_vehicles_device, bit k = plane k
 
 
 def _p(a: Optional[np.ndarray]):
@@ -524,6 +525,47 @@ class BatchedDispatchEnv:
         arrs = [np.zeros(V, dtype=np.int32) for _ in range(4)]
         self._chk(self._lib.vds_read_vehicles(self._h, int(replica), _p(st), *[_p(a) for a in arrs]))
         return dict(state=st, node=arrs[0], cluster=arrs[1], arrive_min=arrs[2], order=arrs[3])
+
+    @staticmethod
+    def _vehicle_planes(state, node, cluster, arrive_min, order, source):
+        want = (state, node, cluster, arrive_min, order, source)
+        return [k for k in range(6) if want[k]]
+
+    def vehicles_device_ptr(self, planes: int = 31) -> int:
+        """Device pointer of the int32 ``[6][R][V]`` block of per-vehicle planes (``vds_vehicles_device``): the planes named by the
+        mask (bit ``k`` = plane ``k`` of ``VEHICLE_PLANE_NAMES``) refreshed from the state as it stands, the others untouched; fixed
+        until the state tables are re-made."""
+        p = C.c_void_p()
+        self._chk(self._lib.vds_vehicles_device(self._h, int(planes), C.byref(p)))
+        return p.value
+
+    def vehicles_torch(self, state=True, node=True, cluster=True, arrive_min=True, order=True, source=False):
+        """``vehicles(r)`` of every replica at once, as zero-copy ``torch`` int32 ``[R, V]`` views on the GPU under the same keys:
+        ``state`` (0 idle, 1 carrying an order, 2 dispatched), ``node`` (LocationNode when idle, DeliveryPoint on the way),
+        ``cluster``, ``arrive_min`` (-1 idle), ``order`` (-1 none) - and ``source`` (the engine's container: 0 idle list, 1 static
+        arrival slot, 2 arrival ring, 3 far list, 4 far inbox).  Only the wanted planes are refreshed and returned.  Asynchronous on
+        the handle's stream; aliases library memory, overwritten by the next vehicles call."""
+        import torch
+
+        ks = self._vehicle_planes(state, node, cluster, arrive_min, order, source)
+        ptr = self.vehicles_device_ptr(sum(1 << k for k in ks))
+
+        class _Block:
+            pass
+
+        blk = _Block()
+        blk.__cuda_array_interface__ = {"shape": (6, self.R, self.V), "typestr": "<i4", "data": (ptr, False), "version": 2, "strides": None}
+        if self.R * self.V == 0:
+            return {VEHICLE_PLANE_NAMES[k]: torch.empty((self.R, self.V), dtype=torch.int32, device=torch.device("cuda", self.device)) for k in ks}
+        t = torch.as_tensor(blk, device=torch.device("cuda", self.device))
+        return {VEHICLE_PLANE_NAMES[k]: t[k] for k in ks}
+
+    def vehicles_all(self, state=True, node=True, cluster=True, arrive_min=True, order=True, source=False) -> Dict[str, np.ndarray]:
+        """``vehicles_torch`` copied to the host (``vds_read_vehicles_all``, synchronous): int32 ``[R, V]`` per wanted plane."""
+        ks = self._vehicle_planes(state, node, cluster, arrive_min, order, source)
+        out = np.empty((len(ks), self.R, self.V), dtype=np.int32)
+        self._chk(self._lib.vds_read_vehicles_all(self._h, sum(1 << k for k in ks), _p(out)))
+        return {VEHICLE_PLANE_NAMES[k]: out[i] for i, k in enumerate(ks)}
 
     def work(self) -> Dict[str, int]:
         out = np.zeros(8, dtype=np.int64)
