@@ -210,6 +210,33 @@ int vds_apply_dispatch_ex(vds_handle *h, int32_t n, const int32_t *replica, cons
  * sticky dispatch error reported by the next vds_sync / vds_read_*; the action is skipped. */
 int vds_apply_dispatch_device(vds_handle *h, int32_t K, const void *dev_actions);
 
+/* Per-vehicle dispatch: one target node per vehicle, for every replica at once, from a DEVICE-resident tensor - what a policy that
+ * decides per vehicle on the planes of vds_vehicles_device emits.  dev_targets: int32 [replicas][V], indexed by the caller's replica
+ * index and by vehicle number (the position in self.Vehicles, as in vds_read_vehicles).  One call is this DispatchFunction body
+ * (:893-898), run in every replica r:
+ *     for v in self.Vehicles:                       # ascending vehicle number
+ *         n = dev_targets[r][v]
+ *         if n >= 0 and v in v.Cluster.IdleVehicles:
+ *             v.Cluster.IdleVehicles.remove(v)        # order of the others preserved
+ *             Clusters[NodeID2Cluster[n]].VehiclesArrivetime[v] = RealExpTime + RoadCost(v.LocationNode, n)
+ *             v.DeliveryPoint = n;  self.DispatchNum += 1;  self.TotallyDispatchCost += cost
+ * - vds_apply_dispatch with one action per such vehicle, given in ascending vehicle order.
+ *   - Dict insertion order among the call's entries is ascending vehicle number, whichever clusters the vehicles leave.
+ *   - Entries of earlier dispatch calls of the same slot (any form) come before; order-carrying entries of the slot are ordered as
+ *     they are for the other forms.
+ *   - A negative entry means no move.  There is no cap on the moves of a call.
+ *   - The entry of a vehicle that is not idle is never looked at: documented behaviour, not an error.
+ *   - Refused and skipped - nothing of a refused action is posted, the vehicle stays idle where it is, and the sticky dispatch error
+ *     is reported once by the next vds_sync / vds_read_* (VDS_ESTATE), exactly as for vds_apply_dispatch_device: a target >= N; a
+ *     target node in no cluster; a non-negative target of an idle vehicle in a replica whose order day is over
+ *     (vds_load_order_days).  The other moves of the call are applied.
+ *   - Capacity overflows (ring_cap, far_cap: many vehicles sent to one cluster for one slot) stay what they are: VDS_ECAPACITY, sticky.
+ * Must follow vds_step of the current slot and precede vds_advance (VDS_EINVAL otherwise, and for a NULL tensor).  Asynchronous on
+ * the handle's stream, which must be ordered after the producer of the tensor.  A call uses up V dispatch sequence numbers of the
+ * slot; on the dense layout VDS_ECAPACITY when the slot's calls would pass 2^25 of them.  Out of scope: a per-vehicle arrive_min /
+ * counted as in vds_apply_dispatch_ex. */
+int vds_apply_dispatch_vehicles_device(vds_handle *h, const void *dev_targets);
+
 /* `self.step += 1; self.RealExpTime += self.TimePeriods` (:1090-1091). */
 int vds_advance(vds_handle *h);
 
@@ -385,6 +412,20 @@ int vds_run_hooked_idle_heads(vds_handle *h, int32_t L);
 #define VDS_VEH_SOURCE 32
 int vds_vehicles_device(vds_handle *h, int32_t planes, void **dev_ptr);
 int vds_read_vehicles_all(vds_handle *h, int32_t planes, int32_t *out);
+
+/* Sticky switch of vds_run_hooked, like vds_run_hooked_idle_heads: per-vehicle planes and per-vehicle targets inside the hooked day.
+ *   planes       a VDS_VEH_* mask (0 .. 63; 0 - none, the default): every slot of the calls that follow refreshes those planes in
+ *                the block of vds_vehicles_device (the -1 fill included), behind the slot's tick, observation, outcome and idle-head
+ *                nodes and before the policy node - a captured policy reads the vehicles of the slot (get the address from
+ *                vds_vehicles_device before capturing: it is the one the day uses);
+ *   dev_targets  int32 [replicas][V] (NULL - off, the default): applied every slot as vds_apply_dispatch_vehicles_device behind the
+ *                policy node, and behind the action tensor of vds_run_hooked when K > 0 (the slot's K-form entries come first; a slot
+ *                uses up K + V sequence numbers).  With K == 0 the day still dispatches.  On the dense layout vds_run_hooked
+ *                returns VDS_ECAPACITY when K + V would pass 2^25.
+ * The day graph is keyed by the mask and by the addresses of the targets and of the planes block as well.  With replica groups every
+ * group has its own nodes.  Never called, or (0, NULL): vds_run_hooked builds exactly the graph it builds without this switch.
+ * `planes` outside 0 .. 63: VDS_EINVAL. */
+int vds_run_hooked_vehicles(vds_handle *h, int32_t planes, const void *dev_targets);
 
 /* Snapshot and restore of the episode state, with per-replica forking (no reference counterpart: a Simulation cannot go back; the
  * nearest thing is Reload + replaying the day, simulator.py:130-212, :1048-1091).

@@ -1,0 +1,627 @@
+"""Per-vehicle dispatch on the device (vds_apply_dispatch_vehicles_device / vds_run_hooked_vehicles; ``env.apply_dispatch_vehicles_torch``,
+``env.run_hooked(vehicle_planes=, vehicle_targets=)``): one target node per vehicle, int32 [R, V].  The oracle step of a call is
+``o.dispatch(ids, targets[r][ids])`` with ``ids`` the ascending vehicle numbers that are idle in the oracle and have a non-negative
+target.  After every call each replica is compared with its own oracle: idle lists, arrival dicts in container order, the
+per-vehicle planes of every replica, DispatchNum and TotallyDispatchCost."""
+import random
+
+import numpy as np
+import pytest
+
+from helpers import load_golden, make_oracle
+from test_gpu_parity import MODES, check_lists, make_env
+from test_gpu_replica_days import mk_env, mk_oracle, synth_days
+from test_gpu_vehicle_planes import check_oracle
+from vehicles_dispatch_simulator_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+R3 = 3
+VDS_EINVAL = -1
+# mass moves send many vehicles to one (cluster, slot): tables of at least V entries instead of the defaults sized for the order flow
+CAPS = dict(idle_cap=256, ring_cap=256, far_cap=256)
+
+
+def torch_stream_kw():
+    import torch
+    return dict(stream=torch.cuda.current_stream().cuda_stream)
+
+
+def to_dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).cuda()
+
+
+def seeded_init(g, R):
+    V, N = int(g["V"]), int(g["N"])
+    valid = g["node2cluster"] >= 0
+    return np.stack([synth.init_vehicle_nodes(random.Random(2000 + r), N, V, valid) for r in range(R)]).astype(np.int32)
+
+
+def make_oracles(g, init, days=None):
+    out = []
+    for r in range(len(init)):
+        o = make_oracle(g) if days is None else mk_oracle(g, days[r])
+        o.reset(init[r])
+        out.append(o)
+    return out
+
+
+def idle_mask(o):
+    L = o.lists()
+    m = np.zeros(o.V, dtype=bool)
+    m[L["idle_veh"][:L["idle_off"][-1]]] = True
+    return m
+
+
+def oracle_apply(o, row):
+    """One call in the oracle; returns (moves, entries that named a vehicle on its way)."""
+    idle = idle_mask(o)
+    ids = np.flatnonzero(idle & (row >= 0))
+    if ids.size:
+        o.dispatch(ids, row[ids])
+    return int(ids.size), int((~idle & (row >= 0)).sum())
+
+
+def check_all(env, oracles, t, tag, replicas=None):
+    """Every replica against its oracle; returns the containers (VDS_VEH_SOURCE) that held dispatched vehicles."""
+    cn = env.counters()
+    planes = env.vehicles_all(source=True)
+    held = set(np.unique(planes["source"][planes["state"] == 2]).tolist())
+    for r, o in enumerate(oracles):
+        if o is None or (replicas is not None and r not in replicas):
+            continue
+        check_lists(env, r, o, t)
+        check_oracle({k: planes[k][r] for k in planes}, o, env.V, env.C, "%s slot %d replica %d" % (tag, t, r))
+        oc = o.counters()
+        assert (cn[r, 4], cn[r, 5]) == (oc["dispatch_num"], oc["dispatch_cost"]), (tag, t, r, cn[r, 4:6], oc)
+    return held
+
+
+def random_targets(rng, g, R, frac=0.25):
+    """About `frac` of all vehicles - idle or not, different per replica - get a random valid node."""
+    V = int(g["V"])
+    valid = np.flatnonzero(g["node2cluster"] >= 0)
+    tg = np.full((R, V), -1, dtype=np.int32)
+    pick = rng.random((R, V)) < frac
+    tg[pick] = valid[rng.integers(0, valid.size, int(pick.sum()))]
+    return tg
+
+
+def late_orders(g):
+    """The fixture with the first order and the orders of the last part of the day only: the slots in between process nothing."""
+    g = dict(g)
+    rel = g["o_release_min"]
+    keep = rel >= rel.min() + 900
+    keep[int(np.argmin(rel))] = True
+    for k in ("o_release_min", "o_pickup", "o_delivery"):
+        g[k] = g[k][keep]
+    return g
+
+
+# ---- 1 / 8. the day walk -------------------------------------------------------------------------------------------------------------
+def walk(name, mode, slots=None, seed=5):
+    g = load_golden(name)
+    env = make_env(g, R3, **{**MODES[mode], **CAPS, **torch_stream_kw()})
+    init = seeded_init(g, R3)
+    env.reset(init)
+    oracles = make_oracles(g, init)
+    rng = np.random.default_rng(seed)
+    T = env.T if slots is None else slots
+    moved = in_flight = 0
+    held = set()
+    for t in range(T):
+        env.step()
+        for o in oracles:
+            o.begin_tick()
+        tg = random_targets(rng, g, R3)
+        env.apply_dispatch_vehicles_torch(to_dev(tg))
+        for r, o in enumerate(oracles):
+            m, f = oracle_apply(o, tg[r])
+            moved += m; in_flight += f
+        held |= check_all(env, oracles, t, "%s %s" % (name, mode))
+        env.advance()
+        for o in oracles:
+            o.end_tick()
+    check_all(env, oracles, T, "%s %s after the last advance" % (name, mode))
+    od = env.orders()
+    for r, o in enumerate(oracles):
+        oo = o.orders()
+        for k in ("status", "vehicle", "wait"):
+            np.testing.assert_array_equal(od[k][r], oo[k], err_msg="replica %d %s" % (r, k))
+    layout = env.layout()
+    env.close()
+    assert moved >= 2 * T and in_flight > 0, (moved, in_flight)      # targets on vehicles in flight occurred and were ignored
+    return layout, held
+
+
+WALKS = [(n, m) for n in ("tiny_kmeans", "tiny_dispatch", "tiny_tick5") for m in ("fast", "rows", "generic", "dense_ring")] + \
+        [(n, m) for n in ("tiny_grid", "tiny_kmeans") for m in ("far", "dense_far")]
+
+
+@pytest.mark.parametrize("name,mode", WALKS)
+def test_day_walk(name, mode):
+    layout, held = walk(name, mode)
+    # dispatched vehicles sat in the arrival ring (2) and, where trips outlive a two-slot ring, in the far inbox (4) and the far list (3)
+    assert held == ({2, 3, 4} if mode in ("far", "dense_far") else {2}), held
+    if name == "tiny_kmeans" and mode in ("fast", "rows", "generic", "dense_ring"):      # (both layouts are walked)
+        assert layout["dense"] == (0 if mode in ("rows", "generic") else 1), layout
+
+
+@pytest.mark.parametrize("mode", ["fast", "dfs_wide"])
+def test_stamp_form_walk(mode):
+    layout, _ = walk("tiny_kmeans_dfs2", mode, slots=10)
+    assert layout["dense_st"] == (1 if mode == "fast" else 0), layout
+
+
+# ---- 2. chunk boundaries -------------------------------------------------------------------------------------------------------------
+CHUNK_CASES = {"first": [0], "chunk_edge": [63, 64], "second_edge_and_last": [127, 128, 139], "every_second": list(range(0, 140, 2)),
+               "all": list(range(140)), "none": [], "first_chunk": list(range(64))}
+
+
+@pytest.fixture(scope="module")
+def chunk_env():
+    g = late_orders(load_golden("tiny_kmeans"))
+    n2c = g["node2cluster"]
+    V, C = int(g["V"]), int(g["C"])
+    sizes = np.bincount(n2c, minlength=C)
+    first_picks = set(n2c[g["o_pickup"][g["o_release_min"] < g["o_release_min"].min() + 10]].tolist())      # (slot 0 takes no vehicle of the long list)
+    big = int(max((c for c in range(C) if c not in first_picks), key=lambda c: sizes[c]))
+    nodes_big, nodes_rest = np.flatnonzero(n2c == big), np.flatnonzero((n2c != big) & (n2c >= 0))
+    init = np.empty((R3, V), dtype=np.int32)
+    for r in range(R3):
+        veh = (np.arange(V) + 3 * r) % V          # the 140 vehicles of the long list differ per replica
+        init[r, veh[:140]] = nodes_big[(np.arange(140) * (r + 1)) % nodes_big.size]
+        init[r, veh[140:]] = nodes_rest[(np.arange(V - 140) * 7 + r) % nodes_rest.size]
+    envs = {mode: make_env(g, R3, **{**MODES[mode], **CAPS, **torch_stream_kw()}) for mode in ("fast", "rows")}
+    yield g, init, big, envs
+    for e in envs.values():
+        e.close()
+
+
+@pytest.mark.parametrize("mode", ["fast", "rows"])
+@pytest.mark.parametrize("case", list(CHUNK_CASES))
+def test_chunk_boundaries(chunk_env, case, mode):
+    g, init, big, envs = chunk_env
+    env = envs[mode]
+    V = int(g["V"])
+    env.reset(init)
+    oracles = make_oracles(g, init)
+    env.step()
+    for o in oracles:
+        o.begin_tick()
+    rng = np.random.default_rng(11)
+    other = np.flatnonzero((g["node2cluster"] != big) & (g["node2cluster"] >= 0))
+    tg = np.full((R3, V), -1, dtype=np.int32)
+    survivors = []
+    for r, o in enumerate(oracles):
+        L = o.lists()
+        seg = L["idle_veh"][L["idle_off"][big]:L["idle_off"][big + 1]]
+        assert seg.size == 140                    # three chunks: 64 + 64 + 12
+        movers = seg[CHUNK_CASES[case]]
+        tg[r, movers] = other[rng.integers(0, other.size, movers.size)]
+        survivors.append(np.delete(seg, CHUNK_CASES[case]))
+    before = [env.lists(r) for r in range(R3)]
+    cn0 = env.counters()
+    env.apply_dispatch_vehicles_torch(to_dev(tg))
+    for r, o in enumerate(oracles):
+        assert oracle_apply(o, tg[r])[0] == len(CHUNK_CASES[case])
+    check_all(env, oracles, 0, case)
+    ob = env.obs()
+    for r in range(R3):
+        G = env.lists(r)
+        np.testing.assert_array_equal(G["idle_veh"][G["idle_off"][big]:G["idle_off"][big + 1]], survivors[r])      # survivors keep their order
+        assert ob["idle_now"][r, big] == survivors[r].size == 140 - len(CHUNK_CASES[case])
+        if case == "none":
+            for k in before[r]:
+                np.testing.assert_array_equal(G[k], before[r][k], err_msg=k)
+    if case == "none":
+        np.testing.assert_array_equal(env.counters(), cn0)
+    # a K-form call behind it: its entries come behind the vehicle form's, whatever that one moved
+    acts = np.full((R3, 2, 3), -1, dtype=np.int32)
+    for r, o in enumerate(oracles):
+        L = o.lists()
+        n = L["idle_off"][big + 1] - L["idle_off"][big]
+        if n >= 2:
+            acts[r, 0] = (big, 1, other[0]); acts[r, 1] = (big, 0, other[0])
+            seg = L["idle_veh"][L["idle_off"][big]:L["idle_off"][big + 1]]
+            o.dispatch(seg[[1, 0]], np.full(2, other[0]))
+    env.apply_dispatch_torch(to_dev(acts))
+    check_all(env, oracles, 0, case + " + K-form")
+    env.advance()
+    env.sync()
+
+
+# ---- 3. insertion order across source clusters -----------------------------------------------------------------------------------------
+def find_order_case(g, o):
+    """(target node, v_lo, v_hi, v_k): v_hi idle in cluster 0, v_lo < v_hi idle in a higher cluster, v_k > v_hi idle anywhere, all
+    arriving at the target in the same slot."""
+    cost, n2c, tick = g["cost"], g["node2cluster"], 10
+    loc, cl = o.vehicles()["loc"], o.vehicles()["cluster"]
+    idle = np.flatnonzero(idle_mask(o))
+    for n in np.flatnonzero(n2c >= 0):
+        d = np.maximum((cost[n, loc[idle]] + tick - 1) // tick, 1)
+        for v_hi in idle[cl[idle] == 0]:
+            same = idle[d == d[idle == v_hi][0]]
+            lo = same[(same < v_hi) & (cl[same] > 0)]
+            k = same[same > v_hi]
+            if lo.size and k.size:
+                return int(n), int(lo[0]), int(v_hi), int(k[-1]), int(d[idle == v_hi][0])
+    raise AssertionError("no such vehicles")
+
+
+@pytest.mark.parametrize("mode", ["fast", "rows"])
+def test_insertion_order_across_source_clusters(mode):
+    g = late_orders(load_golden("tiny_kmeans"))
+    V = int(g["V"])
+    init = seeded_init(g, R3)
+    env = make_env(g, R3, **{**MODES[mode], **CAPS, **torch_stream_kw()})
+    for with_k in (False, True):
+        env.reset(init)
+        oracles = make_oracles(g, init)
+        env.step()
+        for o in oracles:
+            o.begin_tick()
+        n, v_lo, v_hi, v_k, d = find_order_case(g, oracles[0])
+        assert d < 40
+        ct = int(g["node2cluster"][n])
+        tg = np.full((R3, V), -1, dtype=np.int32)
+        tg[0, [v_lo, v_hi]] = n
+        expect = [v_lo, v_hi]
+        if with_k:        # the K-form call first, into the same cluster and slot, on a vehicle with a HIGHER number: its entry comes first
+            L = oracles[0].lists()
+            c_k = int(oracles[0].vehicles()["cluster"][v_k])
+            seg = L["idle_veh"][L["idle_off"][c_k]:L["idle_off"][c_k + 1]]
+            acts = np.full((R3, 1, 3), -1, dtype=np.int32)
+            acts[0, 0] = (c_k, int(np.flatnonzero(seg == v_k)[0]), n)
+            env.apply_dispatch_torch(to_dev(acts))
+            oracles[0].dispatch(np.array([v_k]), np.array([n]))
+            expect = [v_k, v_lo, v_hi]
+        env.apply_dispatch_vehicles_torch(to_dev(tg))
+        assert oracle_apply(oracles[0], tg[0]) == (2, 0)
+        check_all(env, oracles, 0, "order")
+        G = env.lists(0)
+        arr = G["arr_veh"][G["arr_off"][ct]:G["arr_off"][ct + 1]]
+        assert [v for v in arr.tolist() if v in expect] == expect
+        for t in range(1, d + 1):      # ... and they enter the idle list in that order at the arrival slot
+            env.advance()
+            for o in oracles:
+                o.end_tick()
+            env.step()
+            for o in oracles:
+                o.begin_tick()
+        check_all(env, oracles, d, "order at arrival")
+        G = env.lists(0)
+        lst = G["idle_veh"][G["idle_off"][ct]:G["idle_off"][ct + 1]]
+        assert [v for v in lst.tolist() if v in expect] == expect
+        env.advance()
+    env.close()
+
+
+# ---- 4. refusals -----------------------------------------------------------------------------------------------------------------------
+def test_refused_targets_are_skipped_and_reported_once():
+    g = load_golden("tiny_focus_grid")
+    V, N = int(g["V"]), int(g["N"])
+    outside = np.flatnonzero(g["node2cluster"] < 0)
+    assert outside.size == 205
+    init = seeded_init(g, R3)
+    env = make_env(g, R3, **{**CAPS, **torch_stream_kw()})
+    env.reset(init)
+    oracles = make_oracles(g, init)
+    env.step()
+    for o in oracles:
+        o.begin_tick()
+    idle = np.flatnonzero(idle_mask(oracles[1]))
+    good = int(np.flatnonzero(g["node2cluster"] >= 0)[17])
+    tg = np.full((R3, V), -1, dtype=np.int32)
+    tg[1, idle[0]], tg[1, idle[1]], tg[1, idle[2]] = outside[3], N, good
+    env.apply_dispatch_vehicles_torch(to_dev(tg))
+    oracles[1].dispatch(idle[2:3], np.array([good]))
+    with pytest.raises(Exception, match="dispatch"):
+        env.sync()
+    env.sync()                                     # reported once
+    check_all(env, oracles, 0, "refusals")
+    assert env.counters()[1, 4] == 1
+    env.advance()
+    env.close()
+
+
+def test_host_side_argument_checks():
+    import torch
+    g = load_golden("tiny_kmeans")
+    V = int(g["V"])
+    init = seeded_init(g, R3)
+    env = make_env(g, R3, **{**CAPS, **torch_stream_kw()})
+    env.reset(init)
+    good = torch.full((R3, V), -1, dtype=torch.int32, device="cuda")
+    ptr = env._vehicle_targets_ptr(good, "test")
+    assert env._lib.vds_apply_dispatch_vehicles_device(env._h, ptr) == VDS_EINVAL          # before step()
+    assert "vds_step" in env._lib.vds_last_error(env._h).decode()
+    env.step()
+    before = [env.lists(r) for r in range(R3)]
+    moving = torch.zeros((R3, V), dtype=torch.int32, device="cuda")
+    for bad in (moving.to(torch.int64), torch.zeros((R3, V + 1), dtype=torch.int32, device="cuda"), torch.zeros((R3 * V,), dtype=torch.int32, device="cuda"),
+                moving.cpu(), torch.zeros((V, R3), dtype=torch.int32, device="cuda").t(), moving.cpu().numpy()):
+        with pytest.raises(Exception, match="apply_dispatch_vehicles_torch"):
+            env.apply_dispatch_vehicles_torch(bad)
+        with pytest.raises(Exception, match="run_hooked"):
+            env.run_hooked(1, vehicle_targets=bad)
+    with pytest.raises(Exception, match="vehicle_planes"):
+        env.run_hooked(1, vehicle_planes=dict(speed=True))
+    assert env._lib.vds_run_hooked_vehicles(env._h, 64, None) == VDS_EINVAL
+    assert env._lib.vds_apply_dispatch_vehicles_device(env._h, None) == VDS_EINVAL
+    for r in range(R3):
+        G = env.lists(r)
+        for k in G:
+            np.testing.assert_array_equal(G[k], before[r][k])
+    env.apply_dispatch_vehicles_torch(good)
+    env.advance()
+    env.sync()
+    env.close()
+
+
+# ---- 5. order days per replica ---------------------------------------------------------------------------------------------------------
+def test_order_days_per_replica_regrouped():
+    g = load_golden("tiny_kmeans")
+    V, R = int(g["V"]), 5
+    days = synth_days(g, 3, seed=321)[1:]          # a whole day and one that ends after five hours
+    replica_day = np.array([0, 1, 0, 1, 1], dtype=np.int32)       # days mixed inside a group of 16: stored regrouped
+    init = seeded_init(g, R)
+    env = mk_env(g, R, **{**CAPS, **torch_stream_kw()})
+    env.load_order_days(days, replica_day)
+    env.reset(init)
+    oracles = make_oracles(g, init, [days[d] for d in replica_day])
+    Ts = [o.num_ticks for o in oracles]
+    assert env.T == max(Ts) and min(Ts) < max(Ts) and Ts[1] == min(Ts)
+    rng = np.random.default_rng(77)
+    frozen = {}
+    t_bad = min(Ts) + 2
+    for t in range(min(Ts) + 6):
+        env.step()
+        live = [r for r in range(R) if t < Ts[r]]
+        for r in live:
+            oracles[r].begin_tick()
+        tg = random_targets(rng, g, R, frac=0.1 + 0.05 * np.arange(R)[:, None])      # a distinct pattern per replica
+        for r in range(R):
+            if r not in live:
+                tg[r] = -1
+        if t == t_bad:     # a non-negative target on an idle vehicle of a replica whose day is over
+            tg[3, np.flatnonzero(idle_mask(oracles[3]))[0]] = int(np.flatnonzero(g["node2cluster"] >= 0)[5])
+            tg[3, np.flatnonzero(~idle_mask(oracles[3]))[:1]] = 0       # (a vehicle on its way there: never looked at)
+        env.apply_dispatch_vehicles_torch(to_dev(tg))
+        for r in live:
+            oracle_apply(oracles[r], tg[r])
+        if t == t_bad:
+            with pytest.raises(Exception, match="dispatch"):
+                env.sync()
+            env.sync()
+        if t % 6 == 0 or t >= min(Ts) - 1:
+            check_all(env, oracles, t, "days", replicas=live)
+            cn = env.counters()
+            for r in range(R):
+                if t == Ts[r] - 1:
+                    frozen[r] = (env.lists(r), cn[r].copy())
+                elif t >= Ts[r]:          # its city stands still, whatever the call named
+                    L1 = env.lists(r)
+                    for k in L1:
+                        np.testing.assert_array_equal(L1[k], frozen[r][0][k], err_msg="replica %d %s" % (r, k))
+                    np.testing.assert_array_equal(cn[r], frozen[r][1])
+        env.advance()
+        for r in live:
+            oracles[r].end_tick()
+    assert len(frozen) == 3
+    env.close()
+
+
+# ---- 6. the day graph ------------------------------------------------------------------------------------------------------------------
+HG_R = 17
+
+
+def rule_targets(g, o, slot, node_of):
+    """The policy restated on the oracle: idle vehicles with v % 7 == slot % 7 in clusters with more than two idle vehicles go to the
+    first node of the next cluster."""
+    V, C = int(g["V"]), int(g["C"])
+    L = o.lists()
+    n = np.diff(L["idle_off"])
+    cl = np.repeat(np.arange(C), n)
+    veh = L["idle_veh"][:L["idle_off"][-1]]
+    tg = np.full(V, -1, dtype=np.int32)
+    go = (veh % 7 == slot % 7) & (n[cl] > 2)
+    tg[veh[go]] = node_of[(cl[go] + 1) % C]
+    return tg
+
+
+def kform_actions(g, o, node_of):
+    """K = 2: the head of cluster 0 to cluster 3's node, the second vehicle of cluster 5 to cluster 1's node - where the lists have them."""
+    L = o.lists()
+    n = np.diff(L["idle_off"])
+    a = np.full((2, 3), -1, dtype=np.int32)
+    vehs, tgts = [], []
+    for k, (c, p, tc) in enumerate(((0, 0, 3), (5, 1, 1))):
+        if n[c] > p:
+            a[k] = (c, p, node_of[tc])
+            vehs.append(L["idle_veh"][L["idle_off"][c] + p]); tgts.append(node_of[tc])
+    return a, np.array(vehs, dtype=np.int32), np.array(tgts, dtype=np.int32)
+
+
+def day_result(env):
+    env.sync()
+    od = env.orders()
+    return dict(lists=[env.lists(r) for r in range(env.R)], counters=env.counters(), status=od["status"], vehicle=od["vehicle"], wait=od["wait"])
+
+
+def assert_same_day(a, b, tag):
+    np.testing.assert_array_equal(a["counters"], b["counters"], err_msg=tag)
+    for k in ("status", "vehicle", "wait"):
+        np.testing.assert_array_equal(a[k], b[k], err_msg=tag + " " + k)
+    for r, (x, y) in enumerate(zip(a["lists"], b["lists"])):
+        for k in x:
+            np.testing.assert_array_equal(x[k], y[k], err_msg="%s replica %d %s" % (tag, r, k))
+
+
+@pytest.mark.parametrize("groups", [1, 2])
+def test_day_graph(groups):
+    import torch
+    g = load_golden("tiny_dispatch")
+    V, C, R = int(g["V"]), int(g["C"]), HG_R
+    n2c = g["node2cluster"]
+    node_of = np.array([np.flatnonzero(n2c == c)[0] for c in range(C)], dtype=np.int32)
+    init = seeded_init(g, R)
+    stream = torch.cuda.current_stream()
+    env = make_env(g, R, stream=stream.cuda_stream, **CAPS)
+    env.set_run_groups(groups, -1)
+    T = env.T
+    env.reset(init)
+    pl = env.vehicles_torch(state=True, node=False, cluster=True, arrive_min=False, order=False)
+    state, cluster = pl["state"], pl["cluster"]
+    targets = torch.full((R, V), -1, dtype=torch.int32, device="cuda")
+    acts = torch.full((R, 2, 3), -1, dtype=torch.int32, device="cuda")
+    slot = torch.zeros(1, dtype=torch.int64, device="cuda")
+    vmod = (torch.arange(V, device="cuda", dtype=torch.int64) % 7)[None, :]
+    node_t = torch.from_numpy(node_of.astype(np.int64)).cuda()
+    ones = torch.ones((R, V), dtype=torch.int64, device="cuda")
+    act0, act1 = torch.tensor([0, 0, int(node_of[3])], device="cuda"), torch.tensor([5, 1, int(node_of[1])], device="cuda")
+    no_act = torch.tensor([-1, -1, -1], device="cuda")
+
+    def policy():
+        idle = state == 0
+        cl = cluster.to(torch.int64).clamp(min=0)
+        cnt = torch.zeros((R, C), dtype=torch.int64, device="cuda").scatter_add_(1, cl, ones * idle)
+        go = idle & (vmod == slot % 7) & (torch.gather(cnt, 1, cl) > 2)
+        tgt = node_t[(cl + 1) % C]
+        targets.copy_(torch.where(go, tgt, torch.full_like(tgt, -1)).to(torch.int32))
+        # the K-form actions of the combined day (left unused by the vehicle-only day)
+        a0 = torch.where((cnt[:, 0] > 0)[:, None], act0, no_act)
+        a1 = torch.where((cnt[:, 5] > 1)[:, None], act1, no_act)
+        acts.copy_(torch.stack([a0, a1], dim=1).to(torch.int32))
+        slot.add_(1)
+
+    side = torch.cuda.Stream()
+    side.wait_stream(stream)
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            policy()
+    stream.wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph(keep_graph=True)
+    with torch.cuda.graph(graph):
+        policy()
+    torch.cuda.synchronize()
+    planes_kw = dict(state=True, cluster=True)
+    obs_off = dict(idle_pre=False, idle_now=False, supply=False, cl_orders=False)
+
+    for with_k in (False, True):
+        tag = "groups %d K-form %s" % (groups, with_k)
+        # (a) one launch
+        env.reset(init); slot.zero_()
+        env.run_hooked(T, actions=acts if with_k else None, policy_graph=graph, vehicle_planes=planes_kw, vehicle_targets=targets, **obs_off)
+        hooked = day_result(env)
+        assert int(slot.item()) == T
+        assert env.vehicles_device_ptr(5) == state.data_ptr()
+        # (b) slot by slot through the entry points
+        env.reset(init); slot.zero_()
+        for t in range(T):
+            env.step()
+            env.vehicles_torch(state=True, node=False, cluster=True, arrive_min=False, order=False)
+            graph.replay()
+            if with_k:
+                env.apply_dispatch_torch(acts)
+            env.apply_dispatch_vehicles_torch(targets)
+            env.advance()
+        stepwise = day_result(env)
+        assert_same_day(hooked, stepwise, tag + ": hooked against stepwise")
+        # (c) the oracle with the rule restated in numpy
+        oracles = make_oracles(g, init)
+        moves = 0
+        for t in range(T):
+            for o in oracles:
+                o.begin_tick()
+                tg = rule_targets(g, o, t, node_of)
+                if with_k:
+                    _, vehs, tgts = kform_actions(g, o, node_of)
+                    if vehs.size:
+                        o.dispatch(vehs, tgts)
+                moves += oracle_apply(o, tg)[0]
+                o.end_tick()
+        assert moves >= 20
+        for r, o in enumerate(oracles):
+            check_lists(env, r, o, T)
+            oo, oc = o.orders(), o.counters()
+            for k in ("status", "vehicle", "wait"):
+                np.testing.assert_array_equal(stepwise[k][r], oo[k], err_msg="%s replica %d %s" % (tag, r, k))
+            assert (stepwise["counters"][r, 4], stepwise["counters"][r, 5]) == (oc["dispatch_num"], oc["dispatch_cost"]), (tag, r)
+            assert stepwise["counters"][r, 0] == oc["order_num"] and stepwise["counters"][r, 1] == oc["reject_num"] and stepwise["counters"][r, 3] == oc["wait_sum"]
+
+    # switched off again: a hooked day equals one on a handle that never switched it on
+    env.reset(init)
+    state.fill_(-7)
+    env.run_hooked(T, **obs_off)
+    off = day_result(env)
+    assert int((state == -7).all().item()) == 1
+    env.close()
+    fresh = make_env(g, R, stream=stream.cuda_stream, **CAPS)
+    fresh.set_run_groups(groups, -1)
+    fresh.reset(init)
+    fresh.run_hooked(T, **obs_off)
+    assert_same_day(off, day_result(fresh), "switched off")
+    assert off["counters"][:, 4].sum() == 0
+    fresh.close()
+
+
+# ---- 7. snapshot -----------------------------------------------------------------------------------------------------------------------
+def read_everything(env):
+    env.sync()
+    od, ob = env.orders(), env.obs()
+    out = dict(counters=env.counters(), clock=np.array(env.clock))
+    out.update({"orders_" + k: v for k, v in od.items()})
+    out.update({"obs_" + k: v for k, v in ob.items()})
+    out.update({"veh_" + k: v for k, v in env.vehicles_all().items()})
+    for r in range(env.R):
+        out.update({"lists%d_%s" % (r, k): v for k, v in env.lists(r).items()})
+    return out
+
+
+def assert_reads_equal(a, b, tag):
+    assert set(a) == set(b)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg="%s: %s" % (tag, k))
+
+
+@pytest.mark.parametrize("mode", ["fast", "rows"])
+def test_snapshot_restore_around_a_vehicle_call(mode):
+    g = load_golden("tiny_kmeans")
+    init = seeded_init(g, R3)
+    env = make_env(g, R3, **{**MODES[mode], **CAPS, **torch_stream_kw()})
+    env.reset(init)
+    oracles = make_oracles(g, init)
+    for t in range(3):
+        env.step()
+        for o in oracles:
+            o.begin_tick()
+        if t < 2:
+            env.advance()
+            for o in oracles:
+                o.end_tick()
+    env.snapshot()
+    at_snapshot = read_everything(env)
+    tg = random_targets(np.random.default_rng(3), g, R3, frac=0.5)
+    acts = np.full((R3, 2, 3), -1, dtype=np.int32)
+    env.apply_dispatch_vehicles_torch(to_dev(tg))
+    for r, o in enumerate(oracles):
+        oracle_apply(o, tg[r])
+        L = o.lists()
+        c = int(np.argmax(np.diff(L["idle_off"])))
+        acts[r, 0] = (c, 0, tg[r].max())
+        o.dispatch(L["idle_veh"][L["idle_off"][c]:L["idle_off"][c] + 1], np.array([tg[r].max()]))
+    after_v = read_everything(env)
+    env.apply_dispatch_torch(to_dev(acts))
+    after_vk = read_everything(env)
+    check_all(env, oracles, 2, "snapshot: first time")
+    env.restore()
+    assert_reads_equal(read_everything(env), at_snapshot, "after restore")
+    env.apply_dispatch_vehicles_torch(to_dev(tg))
+    assert_reads_equal(read_everything(env), after_v, "the same call again")
+    env.apply_dispatch_torch(to_dev(acts))
+    assert_reads_equal(read_everything(env), after_vk, "the K-form call after it")
+    env.advance()
+    env.close()

@@ -63,6 +63,8 @@ SYMBOLS = {
     "vds_apply_dispatch": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP]),
     "vds_apply_dispatch_ex": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "vds_apply_dispatch_device": (C.c_int, [_VP, _I32, _VP]),
+    "vds_apply_dispatch_vehicles_device": (C.c_int, [_VP, _VP]),
+    "vds_run_hooked_vehicles": (C.c_int, [_VP, _I32, _VP]),
     "vds_advance": (C.c_int, [_VP]),
     "vds_run": (C.c_int, [_VP, _I32]),
     "vds_set_run_groups": (C.c_int, [_VP, _I32, _I32]),

@@ -224,6 +224,9 @@ struct vds_handle {
     int *d_veh = nullptr;                    // vds_vehicles_device: int32 [6][R_ext][V], made on the first request (in MEM_STATE)
     int hooked_heads_L = 0;                  // vds_run_hooked_idle_heads: > 0 - every slot of vds_run_hooked refreshes the heads block (sticky)
     const int *hook_heads = nullptr; int hook_heads_L = 0;   // ... and what the graph at hand was built with
+    int hooked_veh_planes = 0;               // vds_run_hooked_vehicles: every slot of vds_run_hooked refreshes these planes of d_veh (sticky; 0: none)
+    const void *hooked_veh_targets = nullptr;    // ... and applies this per-vehicle target tensor behind the policy (sticky; null: off)
+    int hook_veh_planes = 0; const void *hook_veh_targets = nullptr; const int *hook_veh = nullptr;   // ... and what the graph at hand was built with
     const void *hook_actions = nullptr;
     void *hook_policy = nullptr;
     hipStream_t hook_stream = nullptr;
@@ -1723,6 +1726,7 @@ int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger) {
 // planes and before the first group's dispatch.
 static int ensure_outcomes(vds_handle *h);
 static int ensure_idle_heads(vds_handle *h, int L);
+static int ensure_vehicles(vds_handle *h);
 
 static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
     if (policy_graph && h->hook_policy_inst != policy_graph) {
@@ -1736,8 +1740,10 @@ static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int3
         if ((planes & 31) && (rc = vds_obs_device_planes(h, planes & 31, nullptr))) return rc;
         if ((planes & VDS_PLANE_OUTCOMES) && (rc = vds_outcomes_device(h, nullptr))) return rc;
         if (h->hooked_heads_L > 0 && (rc = vds_idle_heads_device(h, h->hooked_heads_L, nullptr))) return rc;
+        if (h->hooked_veh_planes && (rc = vds_vehicles_device(h, h->hooked_veh_planes, nullptr))) return rc;
         if (policy_graph) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
         if (K > 0 && dev_actions && (rc = vds_apply_dispatch_device(h, K, dev_actions))) return rc;
+        if (h->hooked_veh_targets && (rc = vds_apply_dispatch_vehicles_device(h, h->hooked_veh_targets))) return rc;
         if ((rc = vds_advance(h))) return rc;
     }
     return VDS_OK;
@@ -1754,6 +1760,12 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     if (planes & VDS_PLANE_OUTCOMES) { const int rco = ensure_outcomes(h); if (rco) return rco; }
     const int HL = h->hooked_heads_L;
     if (HL > 0) { const int rch = ensure_idle_heads(h, HL); if (rch) return rch; }
+    // per-vehicle planes / targets of the hooked day (vds_run_hooked_vehicles); VT's sequence numbers follow the K-form's inside a slot
+    const int VP = h->S.V > 0 ? h->hooked_veh_planes : 0;
+    const int *VT = h->S.V > 0 ? (const int *)h->hooked_veh_targets : nullptr;
+    if (VP) { const int rcv = ensure_vehicles(h); if (rcv) return rcv; }
+    if (VT && h->S.dense && (long long)K + h->S.V >= (1 << DENSE_ID_BITS))
+        return fail(h, VDS_ECAPACITY, "vds_run_hooked: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
     const bool groupable = run_groups_hybrid(h) || run_groups_plain(h);
     if (!run_graph_on(h) || h->profiling || !groupable) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
     { const int rcs = dev_copy_sync(h); if (rcs) return rcs; }
@@ -1765,7 +1777,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     const int G = h->run_groups > 0 ? std::min(run_group_count(h), RUN_GROUPS_MAX) : 1;
     const bool same = h->hook_exec && h->hook_gen == h->tables_gen && h->hook_t0 == h->t && h->hook_n == n_ticks && h->hook_G == G && h->hook_planes == planes && h->hook_K == K &&
                       h->hook_actions == dev_actions && h->hook_policy == policy_graph && h->hook_stream == h->stream && h->hook_outc == h->d_outc &&
-                      h->hook_heads == (HL > 0 ? h->d_heads : nullptr) && h->hook_heads_L == HL;
+                      h->hook_heads == (HL > 0 ? h->d_heads : nullptr) && h->hook_heads_L == HL &&
+                      h->hook_veh_planes == VP && h->hook_veh_targets == VT && h->hook_veh == (VP ? h->d_veh : nullptr);
     if (!same) {
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
@@ -1781,6 +1794,12 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                 if (planes & VDS_PLANE_OUTCOMES) c.add(emit_slot_outcomes, h->S, h->D, t, 1, h->d_outc, r.lo, r.n);
                 // the heads of the group's idle lists as the tick left them (vds_run_hooked_idle_heads)
                 if (HL > 0) c.add(emit_idle_heads, h->S, h->D, HL, h->d_heads, r.lo, r.n);
+                // the group's per-vehicle planes as the tick left them (vds_run_hooked_vehicles): the -1 fill as a kernel node, then the scatter
+                if (VP) {
+                    c.add(emit_vehicle_fill, h->S, VP, h->d_veh, r.lo, r.n);
+                    c.add(emit_vehicle_lists, h->S, h->D, t, VP, h->d_veh, r.lo, r.n);
+                    if (vehicle_pull_needed(h->S, t)) c.add(emit_vehicle_pull, h->S, h->D, t, VP, h->d_veh, r.lo, r.n);
+                }
             }
             if (policy_graph) {
                 // (the child graph between two EMPTY nodes: with several parents / several children attached to the child-graph node
@@ -1793,6 +1812,10 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                 const Rows r = group_rows(h, gi, G);
                 if (r.n > 0) c.add(emit_dispatch_dense, h->S, h->D, t, K, (const int *)dev_actions, 0, r.lo, r.n);
             }
+            for (int gi = 0; gi < G && VT; ++gi) {
+                const Rows r = group_rows(h, gi, G);
+                if (r.n > 0) c.add(emit_dispatch_vehicles, h->S, h->D, t, VT, K, r.lo, r.n);
+            }
         }
         if (c.err != hipSuccess) {
             (void)hipGraphDestroy(g);
@@ -1800,16 +1823,18 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
             return fail(h, VDS_EHIP, "vds_run_hooked: building the day graph failed: %s", hipGetErrorString(c.err));
         }
         const bool same_shape = h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) && (h->hook_heads_L > 0) == (HL > 0) &&
-                                (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr);
+                                (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr) &&
+                                (h->hook_veh_planes != 0) == (VP != 0) && (h->hook_veh_targets != nullptr) == (VT != nullptr);
         if (!install_graph(h, drop_hook_graph, &h->hook_exec, h->hook_stream, same_shape, g)) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
         h->hook_t0 = h->t; h->hook_n = n_ticks; h->hook_G = G; h->hook_planes = planes; h->hook_K = K; h->hook_actions = dev_actions;
         h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen; h->hook_outc = h->d_outc;
         h->hook_heads = HL > 0 ? h->d_heads : nullptr; h->hook_heads_L = HL;
+        h->hook_veh_planes = VP; h->hook_veh_targets = VT; h->hook_veh = VP ? h->d_veh : nullptr;
     }
     HIPCHK(h, hipGraphLaunch(h->hook_exec, h->stream));
     h->t += n_ticks;
     h->last_stepped = h->t - 1;
-    if (K > 0) { h->dispatch_seq += K * n_ticks; h->seq_tick = -1; }
+    if (K > 0 || VT) { h->dispatch_seq += (K + (VT ? h->S.V : 0)) * n_ticks; h->seq_tick = -1; }
     return VDS_OK;
 }
 
@@ -2320,6 +2345,14 @@ int vds_run_hooked_idle_heads(vds_handle *h, int32_t L) {
     return VDS_OK;
 }
 
+int vds_run_hooked_vehicles(vds_handle *h, int32_t planes, const void *dev_targets) {
+    if (!h) return VDS_EINVAL;
+    if (planes < 0 || planes > 63) return fail(h, VDS_EINVAL, "vds_run_hooked_vehicles: planes = %d is outside 0 (none) .. 63, a mask of the VDS_VEH_* bits", planes);
+    h->hooked_veh_planes = planes;
+    h->hooked_veh_targets = dev_targets;
+    return VDS_OK;
+}
+
 static int read_counters_impl(vds_handle *h, int64_t *out) {
     if (!h || !h->have_reset || !out) return fail(h, VDS_EINVAL, "vds_read_counters: bad argument / call order");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2749,6 +2782,23 @@ static int apply_dispatch_device_impl(vds_handle *h, int32_t K, const void *dev_
     return VDS_OK;
 }
 
+// The DispatchFunction body from one target node per vehicle (k_dispatch_vehicles, vds_dispatch_vehicles.hip): sequence number of a
+// vehicle's entry = the numbers the slot's earlier calls used + its vehicle number; the call uses up V of them.
+static int apply_dispatch_vehicles_device_impl(vds_handle *h, const void *dev_targets) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: call vds_reset first");
+    if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: must follow vds_step of the current tick (the hook runs after Match, :1083)");
+    if (!dev_targets) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: the target tensor is null");
+    if (h->S.V <= 0) return VDS_OK;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
+    if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + h->S.V >= (1 << DENSE_ID_BITS))
+        return fail(h, VDS_ECAPACITY, "vds_apply_dispatch_vehicles_device: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
+    launch_dispatch_vehicles(h->S, h->D, h->t, (const int *)dev_targets, h->dispatch_seq - h->seq_tick0, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->dispatch_seq += h->S.V;
+    return VDS_OK;
+}
+
 // ---- exception-safe entry points
 int vds_dfs_sequences(const int32_t *nbr_off, const int32_t *nbr_idx, int32_t C, int32_t depth_limit,
                       int32_t *seq_off, int32_t *seq, int64_t cap) {
@@ -2876,6 +2926,10 @@ int vds_read_vehicles(vds_handle *h, int32_t replica, uint8_t *state, int32_t *n
 
 int vds_apply_dispatch_device(vds_handle *h, int32_t K, const void *dev_actions) {
     return guarded(h, "vds_apply_dispatch_device", [&] { return apply_dispatch_device_impl(h, K, dev_actions); });
+}
+
+int vds_apply_dispatch_vehicles_device(vds_handle *h, const void *dev_targets) {
+    return guarded(h, "vds_apply_dispatch_vehicles_device", [&] { return apply_dispatch_vehicles_device_impl(h, dev_targets); });
 }
 
 }  // extern "C"

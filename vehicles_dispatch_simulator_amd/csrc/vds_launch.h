@@ -59,10 +59,15 @@ void launch_idle_heads(const Static &S, const State &D, int L, int *heads, hipSt
 // t_last: slot stepped last (-1: none since the reset); planes: bit k = plane k of the int32 [6][R_ext][V] block `out` is wanted (the
 // caller has filled those with -1).  Two kernels, one launcher each (a graph node each): the bucket containers, and - when
 // vehicle_pull_needed - the static arrival slots
+void emit_vehicle_fill(const Emit &e, const Static &S, int planes, int *out, int r_lo, int r_n);      // the -1 fill as a kernel (day graph)
 void emit_vehicle_lists(const Emit &e, const Static &S, const State &D, int t_last, int planes, int *out, int r_lo, int r_n);
 bool vehicle_pull_needed(const Static &S, int t_last);
 void emit_vehicle_pull(const Emit &e, const Static &S, const State &D, int t_last, int planes, int *out, int r_lo, int r_n);
 void launch_vehicle_planes(const Static &S, const State &D, int t_last, int planes, int *out, hipStream_t st);
+// ---- vds_dispatch_vehicles.hip
+// targets: int32 [R_ext][V] target node per vehicle (negative: stay); seq_base: sequence numbers the slot's earlier dispatch calls used
+void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, int seq_base, int r_lo, int r_n);
+void launch_dispatch_vehicles(const Static &S, const State &D, int t, const int *targets, int seq_base, hipStream_t st);
 // ---- vds_snapshot.hip
 // the tables of a snapshot, one launch each: `src` -> `dst` are State views of the live tables and of the store (either way round),
 // map [S.R] stored replica -> stored source replica (null: identity), tdone the slots whose orders have been processed (SNAP_OUT)

@@ -240,6 +240,30 @@ __global__ __launch_bounds__(VP_THREADS) void k_vehicle_pull(Static S, State D, 
         if (fly[u]) veh_store(o, ext[u], (int)(en[u] >> 8), 1, node[u], rec[u].z & 0xFFFF, now0[u] + ry[u] * S.tick_minutes + rs[u].y + rec[u].w, rec[u].x, SRC_PULL);
 }
 
+// The -1 fill of the requested planes as a kernel (the per-slot refresh inside vds_run_hooked's day graph, which carries kernel nodes
+// only; the entry points on a stream fill with hipMemsetAsync): the rows of the replicas [S.r_lo, r_end) (stored order).
+// Grid: x = replica, y = runs of VP_THREADS vehicles.
+__global__ __launch_bounds__(VP_THREADS) void k_vehicle_fill(Static S, int planes, int r_end, int *__restrict__ out) {
+    const int v = (int)blockIdx.y * VP_THREADS + (int)threadIdx.x;
+    const int r = S.r_lo + (int)blockIdx.x;
+    if (v >= S.V || r >= r_end) return;
+    const int ext = S.int2ext ? S.int2ext[r] : r;
+    if (ext < 0) return;
+    const size_t plane = (size_t)S.R_ext * S.V;
+    int *p = out + (size_t)ext * S.V + v;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+        if (planes >> k & 1) p[k * plane] = -1;
+}
+
+void emit_vehicle_fill(const Emit &e, const Static &S0, int planes, int *out, int r_lo, int r_n) {
+    Static S = S0;
+    S.r_lo = r_lo;
+    const int n = r_n > 0 ? r_n : S.R - r_lo;
+    const dim3 grid(n, (S.V + VP_THREADS - 1) / VP_THREADS), block(VP_THREADS);
+    emit_kernel(e, k_vehicle_fill, grid, block, 0, S, planes, r_lo + n, out);
+}
+
 void emit_vehicle_lists(const Emit &e, const Static &S0, const State &D, int t_last, int planes, int *out, int r_lo, int r_n) {
     Static S = S0;
     S.r_lo = r_lo;

@@ -225,6 +225,27 @@ class BatchedDispatchEnv:
             raise Exception("apply_dispatch_torch: expected a contiguous int32 CUDA tensor")
         self._chk(self._lib.vds_apply_dispatch_device(self._h, int(actions.shape[1]), C.c_void_p(actions.data_ptr())))
 
+    def _vehicle_targets_ptr(self, targets, who: str):
+        if not hasattr(targets, "data_ptr") or not hasattr(targets, "is_cuda"):
+            raise Exception("%s: expected a torch tensor, got %s" % (who, type(targets).__name__))
+        if tuple(targets.shape) != (self.R, self.V):
+            raise Exception("%s: expected an int32 tensor [R, V] = [%d, %d], got %s" % (who, self.R, self.V, list(targets.shape)))
+        if str(targets.dtype) != "torch.int32" or not targets.is_cuda or not targets.is_contiguous():
+            raise Exception("%s: expected a contiguous int32 CUDA tensor" % who)
+        if targets.device.index is not None and targets.device.index != self.device:
+            raise Exception("%s: the tensor lives on cuda:%d, the handle on cuda:%d" % (who, targets.device.index, self.device))
+        return C.c_void_p(targets.data_ptr())
+
+    def apply_dispatch_vehicles_torch(self, targets):
+        """Per-vehicle dispatch (``vds_apply_dispatch_vehicles_device``): ``targets`` is a contiguous int32 CUDA tensor ``[R, V]`` on
+        the handle's device, ``targets[r, v]`` the node vehicle ``v`` of replica ``r`` goes to (negative: stays) - the answer of a
+        policy written on ``vehicles_torch``.  Only idle vehicles move, in ascending vehicle number (``oracle.dispatch(ids, targets[r,
+        ids])``); the entry of a vehicle on its way is never read.  A target ``>= N``, a target node in no cluster or a target in a
+        replica whose order day is over is skipped and raises once at the next ``sync`` / read.  Asynchronous, no host copy; the
+        tensor must stay alive until the handle's stream has passed the call and must have been produced on (or synchronised with)
+        that stream - as for ``apply_dispatch_torch``."""
+        self._chk(self._lib.vds_apply_dispatch_vehicles_device(self._h, self._vehicle_targets_ptr(targets, "apply_dispatch_vehicles_torch")))
+
     def advance(self):
         self._chk(self._lib.vds_advance(self._h))
 
@@ -273,14 +294,21 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_run(self._h, int(n_ticks)))
 
     def run_hooked(self, n_ticks: int, actions=None, policy_graph=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False,
-                   outcomes=False, idle_heads=0):
+                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None):
         """``n_ticks`` slots of ``SimCity`` WITH the dispatch hook on the device as one graph launch (``vds_run_hooked``): per slot
         step -> the named observation planes into the block ``obs_torch`` returns (``outcomes=True``: also the slot's per-cluster
         order outcomes into the block ``outcomes_torch`` returns; ``idle_heads=L``: also the first ``L`` entries of every idle list
         into the block ``idle_heads_torch(L)`` returns - ``0`` switches that off again) -> ``policy_graph`` -> ``actions`` applied ->
         advance.  ``actions``: the contiguous int32 CUDA tensor ``[R, K, 3]`` the policy writes (``None``: no dispatch).
         ``policy_graph``: a ``torch.cuda.CUDAGraph`` captured with ``keep_graph=True`` (its ``raw_cuda_graph()`` is embedded), or a
-        raw ``hipGraph_t`` as an integer, or ``None`` (the tensor is applied as it stands)."""
+        raw ``hipGraph_t`` as an integer, or ``None`` (the tensor is applied as it stands).
+        ``vehicle_planes`` (``vds_run_hooked_vehicles``): the per-vehicle planes every slot refreshes before the policy, in the block
+        ``vehicles_torch`` returns - a dict of ``vehicles_torch``'s flags (``dict(state=True, cluster=True)``; planes not named are
+        off), a sequence of plane names, or a mask of bits ``k`` = plane ``k`` of ``VEHICLE_PLANE_NAMES``; ``None`` / 0: none.  Capture
+        the policy against ``vehicles_torch(...)`` / ``vehicles_device_ptr(mask)`` taken before: the day uses that block.
+        ``vehicle_targets``: the contiguous int32 CUDA tensor ``[R, V]`` the policy writes, applied every slot as
+        ``apply_dispatch_vehicles_torch`` behind the policy and behind ``actions`` (``None``: off).  Both are switched off again by
+        a call without them."""
         planes = (1 if idle_pre else 0) | (2 if idle_now else 0) | (4 if supply else 0) | (8 if cl_orders else 0) | (16 if inflight else 0)
         planes |= PLANE_OUTCOMES if outcomes else 0
         K, ptr = 0, None
@@ -294,6 +322,8 @@ class BatchedDispatchEnv:
         if policy_graph is not None:
             raw = policy_graph if isinstance(policy_graph, int) else int(policy_graph.raw_cuda_graph())
         self._chk(self._lib.vds_run_hooked_idle_heads(self._h, int(idle_heads)))
+        vt = None if vehicle_targets is None else self._vehicle_targets_ptr(vehicle_targets, "run_hooked")
+        self._chk(self._lib.vds_run_hooked_vehicles(self._h, self._vehicle_mask(vehicle_planes), vt))
         self._chk(self._lib.vds_run_hooked(self._h, int(n_ticks), planes, K, ptr, C.c_void_p(raw) if raw is not None else None))
 
     def run_hooked_invalidate(self):
@@ -530,6 +560,21 @@ class BatchedDispatchEnv:
     def _vehicle_planes(state, node, cluster, arrive_min, order, source):
         want = (state, node, cluster, arrive_min, order, source)
         return [k for k in range(6) if want[k]]
+
+    @staticmethod
+    def _vehicle_mask(planes) -> int:
+        """``run_hooked(vehicle_planes=...)``: ``None`` / a mask / a dict of ``vehicles_torch``'s flags / a sequence of plane names."""
+        if planes is None:
+            return 0
+        if isinstance(planes, (int, np.integer)) and not isinstance(planes, bool):
+            if not 0 <= int(planes) <= 63:
+                raise Exception("vehicle_planes: a mask is 0 .. 63, got %d" % int(planes))
+            return int(planes)
+        names = [k for k, on in planes.items() if on] if isinstance(planes, dict) else list(planes)
+        for k in names:
+            if k not in VEHICLE_PLANE_NAMES:
+                raise Exception("vehicle_planes: unknown plane %r (one of %s)" % (k, ", ".join(VEHICLE_PLANE_NAMES)))
+        return sum(1 << VEHICLE_PLANE_NAMES.index(k) for k in set(names))
 
     def vehicles_device_ptr(self, planes: int = 31) -> int:
         """Device pointer of the int32 ``[6][R][V]`` block of per-vehicle planes (``vds_vehicles_device``): the planes named by the
