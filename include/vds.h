@@ -231,7 +231,8 @@ int vds_apply_dispatch_device(vds_handle *h, int32_t K, const void *dev_actions)
  *     target node in no cluster; a non-negative target of an idle vehicle in a replica whose order day is over
  *     (vds_load_order_days).  The other moves of the call are applied.
  *   - Capacity overflows (ring_cap, far_cap: many vehicles sent to one cluster for one slot) stay what they are: VDS_ECAPACITY, sticky.
- * Must follow vds_step of the current slot and precede vds_advance (VDS_EINVAL otherwise, and for a NULL tensor).  Asynchronous on
+ * Must follow vds_step of the current slot and precede vds_advance (VDS_EINVAL otherwise, and for a NULL tensor - except with V == 0,
+ * where the call is a no-op and dev_targets, a tensor without elements, is not looked at).  Asynchronous on
  * the handle's stream, which must be ordered after the producer of the tensor.  A call uses up V dispatch sequence numbers of the
  * slot; on the dense layout VDS_ECAPACITY when the slot's calls would pass 2^25 of them.  Out of scope: a per-vehicle arrive_min /
  * counted as in vds_apply_dispatch_ex. */

@@ -10,6 +10,13 @@ restored replica is a fresh one replayed on the lineage of its source.  The scri
 come from the model's lists), never from what the engine answers: the same seed gives the same calls on every engine, which is
 what lets ``tests/test_api_script_model.py`` prove the harness on a stand-in engine without a GPU.
 
+The per-vehicle entry points: ``dispatch_vehicles`` (``apply_dispatch_vehicles_torch``: targets for all replicas, the refusals of
+include/vds.h drawn on purpose), the reads ``vehicles_all`` / ``vehicles_torch`` with random plane masks, and ``run_hooked`` with a mask of
+vehicle planes and a target tensor.  The planes block is host state too: made on first request, re-made with the tables.  The model keeps,
+plane by plane, the view it was handed and what the block last received (``veh_known``) - a plane that a later call does not ask for must
+still hold it - and forgets both at every call that may re-make the tables (any reset, load, map, cap or run-group call): the views are
+dangling then and are not read again.
+
 Snapshot validity follows include/vds.h: VOID after ``load_orders*`` / ``set_replica_days`` / the first supply-in-place request (which
 is made before the first reset here, when there is no snapshot yet) / ``drop_snapshot``; UNKNOWN after what cannot be seen from
 outside - a ``reset`` / ``reset_random`` that may regrow automatic idle tables, ``set_idle_cap`` (which may or may not replace them), any
@@ -45,15 +52,18 @@ COUNTERS = ("order_num", "reject_num", "matched", "wait_sum", "dispatch_num", "d
 PLANES = ("idle_pre", "idle_now", "supply", "cl_orders", "inflight")
 NO_SNAPSHOT = "libvds error -4: .*no snapshot"
 DISPATCH_ERROR = "libvds error -4: dispatch of an idle position"
-READS = ("obs", "obs_torch", "obs_inplace", "counters", "total_counters", "orders", "lists", "vehicles", "idle_heads", "outcomes")
-KINDS = ("step", "dispatch_host", "dispatch_ex", "dispatch_dev", "advance", "run", "run_hooked", "reset", "reset_again", "reset_random",
+READS = ("obs", "obs_torch", "obs_inplace", "counters", "total_counters", "orders", "lists", "vehicles", "idle_heads", "outcomes", "vehicles_all",
+         "vehicles_torch")
+VEH_PLANES = ("state", "node", "cluster", "arrive_min", "order", "source")       # planes of vehicles_torch / vehicles_all, bit k = plane k
+VEH_REFUSALS = ("beyond_n", "no_cluster", "day_over")                             # what a vehicle-form target is refused for (include/vds.h)
+KINDS = ("step", "dispatch_host", "dispatch_ex", "dispatch_dev", "dispatch_vehicles", "advance", "run", "run_hooked", "reset", "reset_again", "reset_random",
          "snapshot", "restore", "restore_torch", "drop_snapshot", "load_orders", "load_order_days", "set_replica_days", "set_run_groups",
          "set_idle_cap") + READS
 # the state-moving classes whose ordered pairs the corpus has to contain (tests/test_api_script_model.py)
 MOVERS = ("step-loop", "run", "run_hooked", "reset", "reset_again", "reset_random", "snapshot", "restore", "load_orders", "load_order_days",
           "set_replica_days", "set_run_groups", "set_idle_cap")
 MOVER_OF = dict({k: k for k in MOVERS}, step="step-loop", dispatch_host="step-loop", dispatch_ex="step-loop", dispatch_dev="step-loop",
-                advance="step-loop", restore_torch="restore")
+                dispatch_vehicles="step-loop", advance="step-loop", restore_torch="restore")
 NEEDS_RESET = ("load_orders", "load_order_days", "set_replica_days", "set_idle_cap")
 
 
@@ -213,7 +223,9 @@ def to_host(x):
 def new_stats():
     return dict(kinds={}, pairs={}, restores=0, restores_unknown=0, restores_void=0, restores_valid=0, restores_valid_ok=0,
                 restore_after_dispatch=0, hook_applied=0, hook_refused=0, run_same=0, run_moved=0, run_after_change=0, run_eager=0, refused_length=0, refused_twice=0,
-                restore_none_ok=0, refused_map_range=0, refused_map_day=0, calls=[], kernels=set(), storage=set(), layouts=set())
+                restore_none_ok=0, refused_map_range=0, refused_map_day=0, refused_veh_beyond_n=0, refused_veh_no_cluster=0, refused_veh_day_over=0,
+                restore_after_vehicle_dispatch=0, hook_veh_applied=0, hook_veh_refused=0, hook_veh_same=0, hook_veh_after_change=0, veh_partial_behind_full=0,
+                calls=[], kernels=set(), storage=set(), layouts=set())
 
 
 def show(v):
@@ -280,7 +292,15 @@ class Script:
         idx = seed % 1000 + (32 if seed >= 1000 else 0)        # (the corpus' scripts 0 .. 47: their wishes go round the pairs evenly)
         self.wishes = [pairs[(idx + 48 * j) % len(pairs)] for j in range(14)]
         self.pending = []
+        self.forced = []                                # kinds that the next draws take (a restore right behind a vehicle-form call, ...)
         self.held, self.held_src = None, None           # the action tensor of the last hooked run on the device, and what it was made from
+        self.held_vt, self.held_vt_src = None, None     # ... and its vehicle-target tensor
+        self.hook_veh_tables = None                     # `tables` at the hooked call of before
+        self.prev_call = None                           # the state-moving call issued last
+        # the per-vehicle planes block as the model knows it: plane -> (the view that aliases the block, what the block last received);
+        # forgotten whenever the tables may have been re-made (the views are then dangling and never read again)
+        self.veh_known = {}
+        self.veh_full = False                           # a vehicles_torch read of all six planes was drawn since the block was forgotten
         self.env = None
         self.open()
 
@@ -300,6 +320,8 @@ class Script:
         rd = self.block_map(len(ids)) if self.rd is None else self.rd
         init = self.fresh_init() if self.init is None else self.init
         self.snap, self.snap_state, self.need_reset, self.lines = None, VOID, 2, None
+        self.forget_vehicle_block()
+        self.held, self.held_src, self.held_vt, self.held_vt_src = None, None, None, None
         self.pending = [("load_orders", dict(day=ids[0])) if len(ids) == 1 else ("load_order_days", dict(days=ids, rd=rd)), ("reset", dict(init=init))]
 
     def reopen(self):
@@ -382,6 +404,64 @@ class Script:
                 src[rows] = self.rng.choice(rows, size=rows.size)
         return src.astype(np.int32)
 
+    def draw_vehicle_targets(self, hooked=False):
+        """int32 [R, V] targets for all replicas from the model alone, vehicles idle or not.  A stepped slot's call: replicas whose day
+        is over name only vehicles on their way (never looked at), and about 40 % of the calls carry ONE entry the engine must refuse
+        - (targets, (replica, kind) or None).  ``hooked``: the tensor of a hooked run, applied at every slot as it stands (whatever it
+        meets there - the model says what): about half of them hold a node >= N or a node in no cluster."""
+        c, rng = self.c, self.rng
+        tg = np.full((c.R, c.V), -1, dtype=np.int32)
+        pick = rng.random((c.R, c.V)) < float(rng.choice([0.05, 0.3, 1.0]))
+        tg[pick] = rng.choice(c.valid, size=int(pick.sum()))
+        outside = np.flatnonzero(c.n2c < 0)
+        if hooked:
+            if c.V and rng.random() < 0.5:
+                for _ in range(int(rng.integers(1, 4))):
+                    bad = int(rng.choice(outside)) if outside.size and rng.random() < 0.5 else c.N + int(rng.choice([0, 9]))
+                    tg[int(rng.integers(0, c.R)), int(rng.integers(0, c.V))] = bad
+            return tg
+        idle, over = [], []
+        for r, ln in enumerate(self.lines):
+            off, veh = ln.idle()
+            idle.append(veh[:int(off[-1])])
+            if not ln.live:
+                tg[r, idle[r]] = -1
+                over.append(r)
+        refused = None
+        if rng.random() < (0.7 if any(idle[r].size for r in over) else 0.4):
+            kinds = [k for k in VEH_REFUSALS if (k != "no_cluster" or outside.size) and (k != "day_over" or any(idle[r].size for r in over))]
+            kind = kinds[int(rng.integers(0, len(kinds)))]
+            if "day_over" in kinds and rng.random() < 0.8:
+                kind = "day_over"
+            rows = [r for r in range(c.R) if idle[r].size and (r in over) == (kind == "day_over")]
+            if rows:
+                r = rows[int(rng.integers(0, len(rows)))]
+                v = int(idle[r][int(rng.integers(0, idle[r].size))])
+                tg[r, v] = {"beyond_n": c.N + int(rng.choice([0, 1, 1000])), "no_cluster": int(rng.choice(outside)) if outside.size else 0,
+                            "day_over": int(rng.choice(c.valid))}[kind]
+                refused = (r, kind)
+        return tg, refused
+
+    def apply_vehicle_targets(self, r, row):
+        """One replica's row of a vehicle-form call in the model (include/vds.h): the ascending idle vehicles with a valid target
+        move; returns (moves, refused entries)."""
+        c, ln = self.c, self.lines[r]
+        off, veh = ln.idle()
+        idle = np.zeros(c.V, dtype=bool)
+        idle[veh[:int(off[-1])]] = True
+        want = idle & (row >= 0)
+        if not ln.live:
+            return 0, int(want.sum())
+        ok = want & (row < c.N)
+        ok[ok] = c.n2c[row[ok]] >= 0
+        ids = np.flatnonzero(ok)
+        if ids.size:
+            ln.dispatch(ids, row[ids])
+        return int(ids.size), int(want.sum() - ids.size)
+
+    def forget_vehicle_block(self):
+        self.veh_known, self.veh_full = {}, False
+
     def weights(self):
         w = {}
         vd = self.snap_state
@@ -396,18 +476,18 @@ class Script:
                 w["restore"] = .2
             return w
         for k in READS:
-            w[k] = .3
+            w[k] = .4
         w.update(reset=.5, reset_again=.8, reset_random=.4, snapshot=1.3, load_orders=.2, load_order_days=.3, set_run_groups=.4, set_idle_cap=.3)
         w["restore"] = {VALID: 2.6, UNKNOWN: .4, VOID: .05}[vd]
         if len(self.days) == 1:
             w["restore_torch"] = {VALID: .9, UNKNOWN: .1, VOID: .03}[vd]
         w["set_replica_days"] = .3 if len(self.days) > 1 else .15
         if self.snap is not None:
-            w["drop_snapshot"] = .9
+            w["drop_snapshot"] = 1.3
         if self.stepped:
             w["advance"] = 4
             if any(int(self.lines[r].idle()[0][-1]) > 0 for r in self.live()):
-                w.update(dispatch_host=2, dispatch_ex=2, dispatch_dev=2.5)
+                w.update(dispatch_host=2, dispatch_ex=2, dispatch_dev=2.5, dispatch_vehicles=2.5)
         elif self.t < self.T:
             w.update(step=5, run=1.6, run_hooked=1.3)
         return w
@@ -419,7 +499,7 @@ class Script:
             if k in MOVER_OF:
                 by_class.setdefault(MOVER_OF[k], []).append(k)
         if self.stepped and not self.need_reset and self.rng.random() < 0.5:      # an open slot is worked on before anything is steered
-            ks = [k for k in ("advance", "dispatch_host", "dispatch_ex", "dispatch_dev") if k in w]
+            ks = [k for k in ("advance", "dispatch_host", "dispatch_ex", "dispatch_dev", "dispatch_vehicles") if k in w]
             p = np.array([w[k] for k in ks], dtype=np.float64)
             return ks[int(self.rng.choice(len(ks), p=p / p.sum()))]
         u = self.rng.random()
@@ -447,7 +527,11 @@ class Script:
         """The next call as (kind, arguments): legal as the model stands, or marked with the refusal it must meet."""
         if self.pending:
             return self.pending.pop(0)
-        c, rng, kind = self.c, self.rng, self.draw_kind()
+        c, rng = self.c, self.rng
+        if self.forced and not self.need_reset and self.lines is not None and self.forced[0] in self.weights():
+            kind = self.forced.pop(0)
+        else:
+            kind, self.forced = self.draw_kind(), []
         a = {}
         if kind == "reset":
             a["init"] = self.draw_init()
@@ -472,7 +556,11 @@ class Script:
             left = self.T - self.t
             u = rng.random()
             gk = self.graph_key
-            if rng.random() < 0.3:
+            short = min(ln.o.num_ticks for ln in self.lines)
+            if self.t < short < self.T and rng.random() < 0.7:
+                n = short - self.t + int(rng.integers(0, 3))      # to the slots where the shortest day is over and the others run
+                self.forced = ["step", "dispatch_vehicles"]
+            elif rng.random() < 0.3:
                 n = int(rng.integers(1, 8))   # eager: no day graph
             elif gk is not None and gk[1] <= left and u < 0.8:
                 n = gk[1]                   # the count of the day graph of before: a replay at the same first slot, else an update in place
@@ -492,7 +580,7 @@ class Script:
             left = self.T - self.t
             hc = self.hook_cache
             if hc is not None and rng.random() < 0.4 and hc["n"] <= left:   # the hooked call of before again (same tensor: same key)
-                a.update(hc)
+                a.update(hc, again=True)
             else:
                 a["n"] = max(1, min(left, int(rng.choice([1, 3, 8, 12, 30, left]))))
                 a["planes"] = int(rng.integers(0, 32))
@@ -508,7 +596,11 @@ class Script:
                             if rng.random() < 0.8:
                                 acts[r, k] = (cls[k], 0, rng.choice(c.valid))
                     a["acts"] = acts
+                a["vplanes"] = int(rng.integers(1, 64)) if rng.random() < 0.5 else 0
+                a["vtargets"] = self.draw_vehicle_targets(hooked=True) if rng.random() < 0.5 and c.V else None
                 self.hook_cache = dict(a)
+                if (a["vplanes"] or a["vtargets"] is not None) and self.t == 0 and rng.random() < 0.35:      # the same hooked day again: the graph's key repeats
+                    self.pending = [("reset_again", {}), ("run_hooked", dict(a, again=True))]
         elif kind in ("dispatch_host", "dispatch_ex"):
             mv = self.draw_moves(4)
             a["moves"] = {r: (m[1], m[2], m[3]) for r, m in mv.items()}
@@ -543,6 +635,10 @@ class Script:
                 for s, act in zip(slots, lst):
                     acts[r, s] = act
             a["acts"] = acts
+        elif kind == "dispatch_vehicles":
+            a["targets"], a["refused"] = self.draw_vehicle_targets()
+            if self.snap_state == VALID and rng.random() < 0.3:
+                self.forced = ["restore"]
         elif kind in ("restore", "restore_torch"):
             vd = self.snap_state
             a["src"], a["expect"] = None, None
@@ -552,7 +648,7 @@ class Script:
             else:
                 rd = np.asarray(self.snap["rd"])
                 how = str(rng.choice(["none", "identity", "perm", "one", "random", "bad"], p=[.5, .04, .09, .08, .07, .22]))
-                if vd == VALID and np.unique(rd).size > 1 and rng.random() < 0.45:
+                if vd == VALID and np.unique(rd).size > 1 and rng.random() < 0.6:
                     how = "bad"
                 if kind == "restore_torch" and how in ("none", "bad"):
                     how = "perm"
@@ -573,8 +669,17 @@ class Script:
                         src[r] = c.R if rng.random() < 0.5 else -1
                         a["expect"] = "libvds error -1: "
                     a["src"] = src
+            if a["expect"] is None and not self.need_reset and rng.random() < 0.3:      # the planes block right behind the restore
+                self.pending.append(("vehicles_torch" if rng.random() < 0.5 else "vehicles_all", dict(mask=int(rng.integers(1, 64)))))
         elif kind == "obs_torch":
             a["planes"] = int(rng.integers(1, 32))
+        elif kind == "vehicles_all":
+            a["mask"] = int(rng.integers(1, 64))
+        elif kind == "vehicles_torch":        # all six planes until a full read was drawn, then mostly some of them
+            full = rng.random() < (0.3 if self.veh_full else 0.6)
+            a["mask"] = 63 if full else int(rng.integers(1, 63))
+            if full and rng.random() < 0.7:
+                self.forced = ["vehicles_torch"]
         elif kind in ("lists", "vehicles"):
             a["r"] = int(rng.integers(0, c.R))
         elif kind == "idle_heads":
@@ -633,6 +738,12 @@ class Script:
         env, c = self.env, self.c
         self.count(kind)
         full = False
+        if kind in MOVER_OF:
+            before, self.prev_call = self.prev_call, kind
+            if kind in ("restore", "restore_torch") and before == "dispatch_vehicles":
+                self.stats["restore_after_vehicle_dispatch"] += 1
+        if kind in ("reset", "reset_again", "reset_random", "set_idle_cap", "set_run_groups") or kind in NEEDS_RESET:
+            self.forget_vehicle_block()         # (whatever may re-make the state tables: the block lives with them)
         if kind == "step":
             env.step()
             for ln in self.lines:
@@ -670,6 +781,18 @@ class Script:
             self.expect_err = a["refused"] is not None
             if a["refused"] is not None:
                 self.stats["refused_" + a["refused"][1]] += 1
+            self.settle()
+            del held
+        elif kind == "dispatch_vehicles":
+            held = to_device(env, a["targets"])
+            env.apply_dispatch_vehicles_torch(held)
+            for r in range(c.R):
+                moves, refused = self.apply_vehicle_targets(r, a["targets"][r])
+                self.dispatched_in_slot = self.dispatched_in_slot or moves > 0
+                assert refused == (a["refused"] is not None and a["refused"][0] == r), "the script drew %s, the model refuses %d entries of replica %d" % (a["refused"], refused, r)
+            self.expect_err = a["refused"] is not None
+            if a["refused"] is not None:
+                self.stats["refused_veh_" + a["refused"][1]] += 1
             self.settle()
             del held
         elif kind == "run":
@@ -792,7 +915,15 @@ class Script:
         heads = env.idle_heads_torch(a["L"]) if a["L"] else None
         if a["acts"] is not None and self.held_src is not a["acts"]:       # (the tensor of before again: the same address, the graph's key)
             self.held, self.held_src = to_device(env, a["acts"]), a["acts"]
-        env.run_hooked(n, actions=self.held if a["acts"] is not None else None, outcomes=a["outcomes"], idle_heads=a["L"], **kw)
+        vp, vt = a.get("vplanes", 0), a.get("vtargets")
+        if vt is not None and self.held_vt_src is not vt:
+            self.held_vt, self.held_vt_src = to_device(env, vt), vt
+        if a.get("again") and (vp or vt is not None):      # the hooked call of before once more: on the same tables, or behind a change
+            self.stats["hook_veh_same" if self.hook_veh_tables == self.tables else "hook_veh_after_change"] += 1
+        self.hook_veh_tables = self.tables
+        vviews = env.vehicles_torch(**{k: bool(vp >> i & 1) for i, k in enumerate(VEH_PLANES)}) if vp else {}      # (the views of the block the day writes)
+        env.run_hooked(n, actions=self.held if a["acts"] is not None else None, outcomes=a["outcomes"], idle_heads=a["L"],
+                       vehicle_planes=vp, vehicle_targets=self.held_vt if vt is not None else None, **kw)
         seen = []
         for r, ln in enumerate(self.lines):
             for k in range(n):
@@ -800,7 +931,7 @@ class Script:
                 last = None
                 if k == n - 1:          # what the slot's planes show: behind the step, before the slot's actions
                     off, veh = ln.idle()
-                    last = dict(live=ln.live, obs=ln.o.obs(), off=off, veh=veh, loc=ln.o.vehicles()["loc"], outc=ln.outc)
+                    last = dict(live=ln.live, obs=ln.o.obs(), off=off, veh=veh, loc=ln.o.vehicles()["loc"], outc=ln.outc, planes=expected_vehicle_planes(c, ln.o))
                 if a["acts"] is not None:
                     todo = [x for x in a["acts"][r] if x[0] >= 0]
                     if todo and not ln.live:
@@ -818,6 +949,12 @@ class Script:
                                 self.stats["hook_refused"] += 1
                         if vs:
                             ln.dispatch(vs, ts)
+                if vt is not None:          # behind the slot's K-form entries
+                    moves, refused = self.apply_vehicle_targets(r, vt[r])
+                    self.stats["hook_veh_applied"] += moves
+                    if refused:
+                        self.expect_err = True
+                        self.stats["hook_veh_refused"] += 1
                 ln.advance()
             seen.append(last)
         self.t += n
@@ -835,6 +972,8 @@ class Script:
                 h = to_host(heads)
                 np.testing.assert_array_equal(h[0, r], hv, err_msg="run_hooked: head vehicles of replica %d" % r)
                 np.testing.assert_array_equal(h[1, r], hn, err_msg="run_hooked: head nodes of replica %d" % r)
+        if vp:          # the requested vehicle planes: the last slot behind the step and before the slot's actions
+            self.check_vehicle_planes("run_hooked", vviews, [s["planes"] for s in seen], device=True)
 
     def restore(self, kind, a):
         env, c, st = self.env, self.c, self.stats
@@ -952,15 +1091,52 @@ class Script:
                 hv, hn = expected_heads(c, off, veh, ln.o.vehicles()["loc"], a["L"])
                 np.testing.assert_array_equal(got["veh"][r], hv, err_msg="idle_heads: replica %d vehicles" % r)
                 np.testing.assert_array_equal(got["node"][r], hn, err_msg="idle_heads: replica %d nodes" % r)
+        elif kind == "vehicles_all":
+            m = a["mask"]
+            got = env.vehicles_all(**{k: bool(m >> i & 1) for i, k in enumerate(VEH_PLANES)})
+            assert list(got) == [k for i, k in enumerate(VEH_PLANES) if m >> i & 1], list(got)
+            self.check_vehicle_planes(kind, got, [expected_vehicle_planes(c, ln.o) for ln in lines], device=False)
+        elif kind == "vehicles_torch":
+            m = a["mask"]
+            if m == 63:
+                self.veh_full = True
+            elif self.veh_full:
+                self.stats["veh_partial_behind_full"] += 1
+            views = env.vehicles_torch(**{k: bool(m >> i & 1) for i, k in enumerate(VEH_PLANES)})
+            env.sync()
+            assert list(views) == [k for i, k in enumerate(VEH_PLANES) if m >> i & 1], list(views)
+            self.check_vehicle_planes(kind, views, [expected_vehicle_planes(c, ln.o) for ln in lines], device=True)
         elif kind == "outcomes":
             got = env.outcomes()
             for r, ln in enumerate(lines):
                 for i, n in enumerate(("served", "rejected", "wait_sum", "value_sum")):
                     np.testing.assert_array_equal(got[n][r], ln.outc[:, i], err_msg="outcomes: replica %d %s" % (r, n))
 
+    def check_vehicle_planes(self, what, got, exp, device):
+        """The planes a vehicles call was asked for ({name: [R, V]}) against the model (``exp``: per replica, expected_vehicle_planes),
+        the ``source`` plane as helpers.check_oracle checks it; every plane of the block that the model knows and that was NOT asked
+        for keeps what the block held.  Then the model notes what the block received (``device``: ``got`` holds views of the block)."""
+        c = self.c
+        for k, dev in self.veh_known.items():
+            if k not in got and c.R * c.V:
+                np.testing.assert_array_equal(to_host(dev[0]), dev[1], err_msg="%s: plane %s was not asked for and does not hold what the block held" % (what, k))
+        for k, v in got.items():
+            h = np.array(to_host(v))
+            assert h.shape == (c.R, c.V) and h.dtype == np.int32, (what, k, h.shape, h.dtype)
+            for r in range(c.R):
+                if k == "source":
+                    idle = exp[r]["state"] == 0
+                    assert ((h[r] == 0) == idle).all() and (h[r][~idle] >= 1).all() and (h[r][~idle] <= 4).all(), "%s: replica %d plane source" % (what, r)
+                else:
+                    np.testing.assert_array_equal(h[r], exp[r][k], err_msg="%s: replica %d plane %s" % (what, r, k))
+            if device:
+                self.veh_known[k] = (v, h)
+            elif k in self.veh_known:       # (the host read refreshes the same block)
+                self.veh_known[k] = (self.veh_known[k][0], h)
+
     def record_state(self, kind):
         """Appends "<call> <kind> <read> <digest>" for every read entry point, each array in full.  Nothing is masked: every plane of
-        the observation block is asked for (include/vds.h leaves only planes NOT asked for unspecified)."""
+        the observation block and all six per-vehicle planes are asked for (include/vds.h leaves only planes NOT asked for unspecified)."""
         env, c = self.env, self.c
 
         def put(name, v):
@@ -993,6 +1169,13 @@ class Script:
         blk = env.idle_heads_torch(RECORD_HEADS_L)
         env.sync()
         put("idle_heads_torch", blk)
+        allv = env.vehicles_all(source=True)         # (refreshes the block; so does the device read: the model notes what it received)
+        put("vehicles_all", allv)
+        views = env.vehicles_torch(source=True)
+        env.sync()
+        put("vehicles_torch", views)
+        for k, v in views.items():
+            self.veh_known[k] = (v, np.array(to_host(v)))
         if hasattr(env, "counters_torch"):
             blk = env.counters_torch()
             env.sync()
@@ -1011,7 +1194,24 @@ class Script:
 
 def corpus():
     """(seeds of the single-handle cases, seed pairs of the two-handle cases) of the GPU corpus; VDS_APISEQ_N: more single ones."""
-    return list(range(int(os.environ.get("VDS_APISEQ_N", "32")))), [(1000 + 2 * i, 1001 + 2 * i) for i in range(8)]
+    return list(range(int(os.environ.get("VDS_APISEQ_N", "40")))), [(1000 + 2 * i, 1001 + 2 * i) for i in range(8)]
+
+
+def expected_vehicle_planes(c, o):
+    """The five per-vehicle planes of one replica from its oracle (include/vds.h: state, node, cluster, arrive_min, order)."""
+    L, veh = o.lists(), o.vehicles()
+    n, na = int(L["idle_off"][-1]), int(L["arr_off"][-1])
+    idle, fly = L["idle_veh"][:n], L["arr_veh"][:na]
+    assert n + na == c.V
+    out = {k: np.full(c.V, -1, dtype=np.int32) for k in VEH_PLANES[:5]}
+    out["state"][idle] = 0
+    out["state"][fly] = np.where(veh["order"][fly] >= 0, 1, 2)
+    out["node"][idle], out["node"][fly] = veh["loc"][idle], veh["dest"][fly]
+    out["cluster"][idle] = np.repeat(np.arange(c.C), np.diff(L["idle_off"]))
+    out["cluster"][fly] = np.repeat(np.arange(c.C), np.diff(L["arr_off"]))
+    out["arrive_min"][fly] = L["arr_min"][:na]
+    out["order"][fly] = veh["order"][fly]
+    return out
 
 
 def expected_heads(c, off, veh, loc, L):

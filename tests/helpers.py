@@ -191,3 +191,75 @@ def fuzz_coverage_gaps(cases):
     need("dispatch with depth >= 2", lambda r: r["dispatch"] and r["nbr"] and r["depth"] >= 2)
     need("nodes outside every cluster with depth >= 1 and a live window", lambda r: r["outside"] and r["nbr"] and r["depth"] >= 1 and r["window"] is not None)
     return gaps
+
+
+# ---- the per-vehicle planes and the per-vehicle dispatch against one oracle (tests/test_gpu_vehicle_planes.py,
+# tests/test_gpu_dispatch_vehicles.py, tests/test_gpu_vehicle_fuzz.py, tests/api_script.py) ----------------------------------------
+def host_view(env, r):
+    """``env.vehicles(r)`` in the planes' form: state widened to int32, 255 -> -1."""
+    W = env.vehicles(r)
+    st = W["state"].astype(np.int32)
+    st[W["state"] == 255] = -1
+    return dict(W, state=st)
+
+
+def check_oracle(P, o, V, C, tag):
+    """The planes of one replica against one oracle: test_gpu_parity.check_lists' per-vehicle assertions."""
+    L, veh = o.lists(), o.vehicles()
+    n, na = L["idle_off"][-1], L["arr_off"][-1]
+    idle = np.zeros(V, dtype=bool); idle[L["idle_veh"][:n]] = True
+    fly = L["arr_veh"][:na]
+    assert ((P["state"] == 0) == idle).all() and set(np.flatnonzero(P["state"] > 0)) == set(fly.tolist()), tag
+    assert n + na == V and (P["state"] >= 0).all(), tag
+    np.testing.assert_array_equal(P["node"][idle], veh["loc"][idle], err_msg=tag)
+    np.testing.assert_array_equal(P["node"][fly], veh["dest"][fly], err_msg=tag)
+    np.testing.assert_array_equal(P["order"][fly], veh["order"][fly], err_msg=tag)
+    np.testing.assert_array_equal(P["state"][fly], np.where(veh["order"][fly] >= 0, 1, 2), err_msg=tag)
+    np.testing.assert_array_equal(P["arrive_min"][fly], L["arr_min"][:na], err_msg=tag)
+    assert (P["arrive_min"][idle] == -1).all() and (P["order"][idle] == -1).all(), tag
+    cl_idle = np.empty(V, dtype=np.int64); cl_idle[L["idle_veh"][:n]] = np.repeat(np.arange(C), np.diff(L["idle_off"]))
+    np.testing.assert_array_equal(P["cluster"][idle], cl_idle[idle], err_msg=tag)
+    cl_fly = np.empty(V, dtype=np.int64); cl_fly[fly] = np.repeat(np.arange(C), np.diff(L["arr_off"]))
+    np.testing.assert_array_equal(P["cluster"][fly], cl_fly[fly], err_msg=tag)
+    if "source" in P:
+        assert ((P["source"] == 0) == idle).all() and (P["source"][fly] >= 1).all() and (P["source"][fly] <= 4).all(), tag
+
+
+def idle_mask(o):
+    L = o.lists()
+    m = np.zeros(o.V, dtype=bool)
+    m[L["idle_veh"][:L["idle_off"][-1]]] = True
+    return m
+
+
+def oracle_apply(o, row):
+    """One call in the oracle; returns (moves, entries that named a vehicle on its way)."""
+    idle = idle_mask(o)
+    ids = np.flatnonzero(idle & (row >= 0))
+    if ids.size:
+        o.dispatch(ids, row[ids])
+    return int(ids.size), int((~idle & (row >= 0)).sum())
+
+
+REFUSALS = ("beyond_n", "no_cluster", "day_over")
+
+
+def oracle_apply_vehicles(o, row, n2c, over=False):
+    """One vehicle-form call of one replica as include/vds.h states it: ``ids`` = the ascending vehicle numbers that are idle in the
+    oracle and have ``0 <= row[v] < N`` with ``n2c[row[v]] >= 0``; the oracle step is ``o.dispatch(ids, row[ids])`` - unless the
+    replica's day is ``over``, when nothing moves.  Returns (moves, {refusal kind: refused entries}): a non-negative target of an
+    idle vehicle that is >= N ("beyond_n"), names a node in no cluster ("no_cluster") or meets a day that is over ("day_over").  Any
+    refused entry means the sticky dispatch error, once, at the next sync or read."""
+    row, n2c = np.asarray(row), np.asarray(n2c)
+    want = idle_mask(o) & (row >= 0)
+    refused = dict.fromkeys(REFUSALS, 0)
+    if over:
+        refused["day_over"] = int(want.sum())
+        return 0, refused
+    beyond = want & (row >= n2c.size)
+    outside = want & ~beyond & (n2c[np.clip(row, 0, n2c.size - 1)] < 0)
+    refused["beyond_n"], refused["no_cluster"] = int(beyond.sum()), int(outside.sum())
+    ids = np.flatnonzero(want & ~beyond & ~outside)
+    if ids.size:
+        o.dispatch(ids, row[ids])
+    return int(ids.size), refused

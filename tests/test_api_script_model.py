@@ -1,7 +1,7 @@
 """The CPU half of the API-sequence tests (tests/api_script.py): the whole harness - generator, model, runner, comparisons - driven
 on ``OracleEnv``, a stand-in for ``BatchedDispatchEnv`` built from CPU oracles alone, for every seed of the GPU corpus
 (tests/test_gpu_api_sequences.py).  It proves, without a GPU, that the harness is green on a correct engine, that the corpus reaches
-the transitions it claims to reach, and that it goes red when the engine is subtly wrong (five seeded faults, one at a time).
+the transitions it claims to reach, and that it goes red when the engine is subtly wrong (eleven seeded faults, one at a time).
 
 ``OracleEnv`` keeps its own books - one event log per replica, replayed into a fresh oracle by a restore - and shares none of the
 model's bookkeeping code (``api_script.Lineage`` keeps dispatches per slot and is replayed slot by slot)."""
@@ -15,7 +15,14 @@ import api_script
 from api_script import MOVERS, KINDS, ScriptFailure, legal_pair, new_stats, run_script
 from oracle.oracle import Oracle
 
-FAULTS = ("restore_source", "stale_run", "drop_last_action", "snapshot_survives_map", "stale_cluster_list")
+FAULTS = ("restore_source", "stale_run", "drop_last_action", "snapshot_survives_map", "stale_cluster_list",
+          # the per-vehicle dispatch and the per-vehicle planes:
+          "veh_descending",             # the vehicle form applied in descending vehicle order
+          "veh_before_kform",           # its entries placed before an earlier K-form call of the same slot
+          "veh_stored_replica",         # the target tensor indexed by the stored rather than the caller's replica under a regrouping map
+          "veh_refused_applied",        # a refused target applied all the same
+          "veh_block_stale_restore",    # the planes block not refreshed after a restore
+          "veh_unrequested_written")    # a plane that was not requested overwritten
 
 
 def _up(x, m):
@@ -81,6 +88,7 @@ class OracleEnv:
         self.snap, self.err = None, False
         self.blocks = {}
         self.cap_changed = False
+        self.veh_stale = False
 
     def oracle(self, day):
         return Oracle(self.cost, self.n2c, self.off, self.idx, self.depth, self.nbr, day[0], day[1], day[2], self.V, **self.okw)
@@ -96,6 +104,7 @@ class OracleEnv:
         if self.days is not None and self.reps is not None:
             self.prev_days = (self.days, self.rd)
         self.days, self.rd, self.reps = days, np.array(rd, dtype=np.int32), None
+        self.blocks.pop("veh", None)        # (the planes block lives with the state tables)
         self.T = max(self.oracle(days[d]).num_ticks for d in set(self.rd.tolist()))
         if not keep_snapshot:
             self.snap = None
@@ -172,12 +181,12 @@ class OracleEnv:
     def step(self):
         assert not self.stepped and self.t < self.T
         self._all(("step",))
-        self.stepped = True
+        self.stepped, self.veh_stale = True, False
 
     def advance(self):
         assert self.stepped
         self._all(("advance",))
-        self.t, self.stepped = self.t + 1, False
+        self.t, self.stepped, self.veh_stale = self.t + 1, False, False
 
     def run(self, n):
         if self.stale_run:              # the day graph of before the load: the previous day's orders
@@ -235,7 +244,50 @@ class OracleEnv:
         for r in range(self.R):
             self._device_actions(r, acts[r])
 
-    def run_hooked(self, n, actions=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False, outcomes=False, idle_heads=0):
+    def _vehicle_row(self, r, row):
+        """One replica's row of a vehicle-form call (include/vds.h): the idle vehicles with a valid target, ascending, as one hook body."""
+        rep = self.reps[r]
+        L = rep.o.lists()
+        idle = np.zeros(self.V, dtype=bool)
+        idle[L["idle_veh"][:L["idle_off"][-1]]] = True
+        want = np.flatnonzero(idle & (row >= 0))
+        if not want.size:
+            return
+        over = rep.t >= rep.T
+        good = [v for v in want if not over and row[v] < self.N and self.n2c[row[v]] >= 0]
+        if len(good) < want.size:
+            self.err = True
+            if self.fault == "veh_refused_applied":     # the day is over, or the node is beyond the city: moved all the same (to node % N)
+                good = [v for v in want if self.n2c[row[v] % self.N] >= 0]
+        veh, tgt = [int(v) for v in good], [int(row[v] % self.N) for v in good]
+        if not veh:
+            return
+        if self.fault == "veh_descending":
+            veh, tgt = veh[::-1], tgt[::-1]
+        ev = ("dispatch", veh, tgt, None, True)
+        first = max(i for i, e in enumerate(rep.log) if e[0] == "step") + 1      # the slot's earlier dispatch calls: rep.log[first:]
+        if self.fault == "veh_before_kform" and len(rep.log) > first:
+            fresh = _Rep(self, rep.init, rep.day)
+            for e in rep.log[:first] + [ev] + rep.log[first:]:
+                fresh.apply(e)
+            self.reps[r] = fresh
+        else:
+            rep.apply(ev)
+
+    def apply_dispatch_vehicles_torch(self, targets):
+        assert self.stepped
+        tg = np.array(targets)
+        assert tg.shape == (self.R, self.V) and tg.dtype == np.int32
+        rows = np.arange(self.R)
+        if self.fault == "veh_stored_replica" and len(set(self.rd.tolist())) > 1:      # stored by day: replica order[i] reads row i
+            order = np.argsort(self.rd, kind="stable")
+            rows = np.empty(self.R, dtype=np.int64)
+            rows[order] = np.arange(self.R)
+        for r in range(self.R):
+            self._vehicle_row(r, tg[rows[r]])
+
+    def run_hooked(self, n, actions=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False, outcomes=False, idle_heads=0,
+                   vehicle_planes=None, vehicle_targets=None):
         assert not self.stepped and self.t + n <= self.T
         for k in range(n):
             self.step()
@@ -245,9 +297,13 @@ class OracleEnv:
                     self.outcomes_torch()
                 if idle_heads:
                     self.idle_heads_torch(idle_heads)
+                if vehicle_planes:
+                    self.vehicles_torch(**{name: bool(vehicle_planes >> i & 1) for i, name in enumerate(api_script.VEH_PLANES)})
             if actions is not None:
                 for r in range(self.R):
                     self._device_actions(r, np.asarray(actions)[r])
+            if vehicle_targets is not None:
+                self.apply_dispatch_vehicles_torch(vehicle_targets)
             self.advance()
 
     def set_run_groups(self, groups=0, stagger=-1):
@@ -291,6 +347,7 @@ class OracleEnv:
                 rep.apply(ev)
             reps.append(rep)
         self.reps, self.t, self.stepped, self.err = reps, self.snap["t"], self.snap["stepped"], False
+        self.veh_stale = self.fault == "veh_block_stale_restore"
 
     def restore_torch(self, src):
         if self.snap is None:
@@ -360,6 +417,22 @@ class OracleEnv:
         node, order, arrive = veh["loc"].copy(), np.full(self.V, -1, np.int32), np.full(self.V, -1, np.int32)
         node[fly], order[fly], arrive[fly] = veh["dest"][fly], veh["order"][fly], L["arr_min"][:na]
         return dict(state=state, node=node, cluster=self.n2c[node], arrive_min=arrive, order=order)
+
+    def vehicles_torch(self, state=True, node=True, cluster=True, arrive_min=True, order=True, source=False):
+        """Views of the int32 [6, R, V] block: the wanted planes refreshed, the others keep what the block held."""
+        blk = self.blocks.setdefault("veh", np.full((6, self.R, self.V), -1, dtype=np.int32))
+        want = (state, node, cluster, arrive_min, order, source)
+        stale, self.veh_stale = self.veh_stale, False
+        for r in range(self.R):
+            W = self.vehicles(r)
+            src = np.where(W["state"] == 0, 0, 2)
+            for i, name in enumerate(api_script.VEH_PLANES):
+                if (want[i] or self.fault == "veh_unrequested_written") and not stale:
+                    blk[i, r] = src if name == "source" else W[name]
+        return {name: blk[i] for i, name in enumerate(api_script.VEH_PLANES) if want[i]}
+
+    def vehicles_all(self, **planes):
+        return {k: v.copy() for k, v in self.vehicles_torch(**planes).items()}
 
     def idle_heads_torch(self, L):
         blk = self.blocks.setdefault(("heads", L), np.zeros((2, self.R, self.C, L), dtype=np.int32))
@@ -458,6 +531,20 @@ def test_thin_spots_of_the_corpus_have_floors():
     assert 2 * st["restores_void"] <= st["restores"], (st["restores_void"], st["restores"])
 
 
+def test_the_vehicle_form_and_the_planes_block_have_floors():
+    """The per-vehicle dispatch like the other forms, each of its refusals, a restore right behind it; hooked days with vehicle
+    targets applied and refused, called again with the same tensors on the same tables and behind a table change; a device read of
+    some planes behind one of all six (what the other planes keep is then known)."""
+    st = corpus_stats()
+    assert st["kinds"]["dispatch_vehicles"] >= 30, st["kinds"]["dispatch_vehicles"]
+    refused = {k: st["refused_veh_" + k] for k in api_script.VEH_REFUSALS}
+    assert min(refused.values()) >= 5, refused
+    assert st["restore_after_vehicle_dispatch"] >= 3, st["restore_after_vehicle_dispatch"]
+    assert st["hook_veh_applied"] >= 10 and st["hook_veh_refused"] >= 10, (st["hook_veh_applied"], st["hook_veh_refused"])
+    assert st["hook_veh_same"] >= 3 and st["hook_veh_after_change"] >= 3, (st["hook_veh_same"], st["hook_veh_after_change"])
+    assert st["veh_partial_behind_full"] >= 5, st["veh_partial_behind_full"]
+
+
 def test_hooked_actions_are_applied_and_refused():
     st = corpus_stats()
     assert st["hook_applied"] >= 10 and st["hook_refused"] >= 10, (st["hook_applied"], st["hook_refused"])
@@ -493,7 +580,7 @@ def test_a_prefix_replays_the_same_calls():
 
 
 RECORDED_READS = ("clock", "snapshot_info", "obs", "counters", "orders", "outcomes", "idle_heads", "lists[0]", "vehicles[0]", "obs_torch",
-                  "obs_inplace_torch", "outcomes_torch", "idle_heads_torch")
+                  "obs_inplace_torch", "outcomes_torch", "idle_heads_torch", "vehicles_all", "vehicles_torch")
 
 
 @pytest.mark.parametrize("seed", corpus_seeds()[:3])

@@ -1,5 +1,5 @@
 """Random API sequences on one handle against the oracle model (tests/api_script.py; its CPU half, with the coverage conditions of
-the corpus and the seeded faults, is tests/test_api_script_model.py): one case per seed on the real ``BatchedDispatchEnv`` - 32 by
+the corpus and the seeded faults, is tests/test_api_script_model.py): one case per seed on the real ``BatchedDispatchEnv`` - 40 by
 default, VDS_APISEQ_N for more - and 8 cases with TWO handles alive at once, each with its own case and model, their calls dealt
 alternately on one stream, the second handle closed and opened again half-way.  Bit-exact, no tolerance.  A case that passed has also
 given back every device block its handles took (``vds_debug_device_blocks`` before the first handle and after the last close).  A red case names its seed,

@@ -20,7 +20,7 @@ byte before first use (``VDS_DIRTY_FILL``, hex, default ``A5``: ``0xA5A5A5A5`` i
 Seconds per leg under the PRODUCT library on an MI355X (one run each, pytest start-up included), from which the limits follow as
 ten times that + 120 s for the build check and start-up - a safety stop, not a measurement:
 
-    a 110   b 53   c 13   d 6   e 15   f 6   g 7   h 9
+    a 110   b 53   c 18   d 6   e 15   f 6   g 7   h 9   i 21
 
 The libraries are built on demand into ``build/`` exactly as tests/test_gpu_debug_builds.py does (content hashes, not file times)."""
 import json
@@ -40,7 +40,7 @@ TESTS = os.path.join(ROOT, "tests")
 LEGS = {
     "a": (110, ["test_gpu_fuzz_golden.py"], None),
     "b": (53, ["test_gpu_plane_fuzz.py"], None),
-    "c": (13, ["test_gpu_api_sequences.py"], None),
+    "c": (18, ["test_gpu_api_sequences.py"], None),
     "d": (6, ["test_gpu_snapshot.py"], "rows_at_capacity"),
     "e": (15, ["test_gpu_thresholds.py"], None),
     "f": (6, ["test_gpu_edge_cases.py"], "reset_again_of_a_city or reset_random or reset_checks"),
@@ -51,6 +51,13 @@ LEGS = {
           "(test_gpu_replica_days and (changes_every_episode or blocks_of_sixteen)) or "
           "(test_gpu_idle_heads and (layout or replica_days or interleaved_days or own_order_stream))"),
     "h": (9, ["test_gpu_device_memory.py"], None),
+    # (i: the per-vehicle planes - "every element of a requested plane is written, whatever the tables hold", include/vds.h - and the
+    # per-vehicle dispatch: the day walks and the odd sizes of the planes file, the day walks and the chunk boundaries of the dispatch
+    # file, the walks of the fuzz file; one -k for three files, each part names its file - test_leg_i_selects_tests_in_each_of_its_files)
+    "i": (21, ["test_gpu_vehicle_planes.py", "test_gpu_dispatch_vehicles.py", "test_gpu_vehicle_fuzz.py"],
+          "(test_gpu_vehicle_planes and (planes_equal_host_view_and_oracle or odd_vehicle_and_replica_counts)) or "
+          "(test_gpu_dispatch_vehicles and (test_day_walk or test_stamp_form_walk or test_chunk_boundaries)) or "
+          "(test_gpu_vehicle_fuzz and walk_planes_and_three_dispatch_forms)"),
 }
 # (leg, fill byte): every leg with the default byte, then the two that reach the most tables with the positive pattern
 RUNS = [(k, None) for k in LEGS] + [("a", "5A"), ("c", "5A")]
@@ -125,6 +132,19 @@ def test_the_fill_is_live_in_the_dirty_build_only():
     assert bid.endswith("+dirty") and rc == 0 and words == ["5A5A5A5A"] * 4, (bid, rc, words)
     bid, rc, words = probe(None, "5A")
     assert bid.count("+") == 1 and rc == -4 and words == ["00000000"] * 4, (bid, rc, words)      # VDS_ESTATE, out untouched
+
+
+def test_leg_i_selects_tests_in_each_of_its_files():
+    """The -k expression of leg i names tests in every one of its three files (collection only: nothing is started on the GPU)."""
+    _, files, select = LEGS["i"]
+    p = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-m", "gpu", "-k", select] + [os.path.join(TESTS, f) for f in files],
+                       capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    ids = [l for l in p.stdout.splitlines() if "::" in l]
+    per_file = {f: [i for i in ids if f + "::" in i] for f in files}
+    assert len(per_file["test_gpu_vehicle_planes.py"]) == 17 + 5, per_file["test_gpu_vehicle_planes.py"]              # the day walks, the odd sizes
+    assert len(per_file["test_gpu_dispatch_vehicles.py"]) == 16 + 2 + 14, per_file["test_gpu_dispatch_vehicles.py"]    # day walks, stamp form, chunk cases
+    assert len(per_file["test_gpu_vehicle_fuzz.py"]) >= 10 and all("test_walk_planes" in i for i in per_file["test_gpu_vehicle_fuzz.py"]), per_file["test_gpu_vehicle_fuzz.py"]
 
 
 @pytest.mark.parametrize("leg,fill", RUNS, ids=[k if f is None else "%s-%s" % (k, f) for k, f in RUNS])

@@ -8,10 +8,9 @@ import random
 import numpy as np
 import pytest
 
-from helpers import load_golden, make_oracle
+from helpers import check_oracle, idle_mask, load_golden, make_oracle, oracle_apply
 from test_gpu_parity import MODES, check_lists, make_env
 from test_gpu_replica_days import mk_env, mk_oracle, synth_days
-from test_gpu_vehicle_planes import check_oracle
 from vehicles_dispatch_simulator_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -45,22 +44,6 @@ def make_oracles(g, init, days=None):
         o.reset(init[r])
         out.append(o)
     return out
-
-
-def idle_mask(o):
-    L = o.lists()
-    m = np.zeros(o.V, dtype=bool)
-    m[L["idle_veh"][:L["idle_off"][-1]]] = True
-    return m
-
-
-def oracle_apply(o, row):
-    """One call in the oracle; returns (moves, entries that named a vehicle on its way)."""
-    idle = idle_mask(o)
-    ids = np.flatnonzero(idle & (row >= 0))
-    if ids.size:
-        o.dispatch(ids, row[ids])
-    return int(ids.size), int((~idle & (row >= 0)).sum())
 
 
 def check_all(env, oracles, t, tag, replicas=None):

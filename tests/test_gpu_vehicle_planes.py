@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 import threshold_cities as tc
-from helpers import dispatch_by_tick, load_golden, make_oracle
+from helpers import check_oracle, dispatch_by_tick, host_view, load_golden, make_oracle
 from test_gpu_parity import MODES, make_env
 from test_gpu_replica_days import mk_env, mk_oracle, synth_days
 from vehicles_dispatch_simulator_amd import _lib, synth
@@ -27,36 +27,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FIELDS = ("state", "node", "cluster", "arrive_min", "order")
 VDS_EINVAL = -1
-
-
-def host_view(env, r):
-    """``env.vehicles(r)`` in the planes' form: state widened to int32, 255 -> -1."""
-    W = env.vehicles(r)
-    st = W["state"].astype(np.int32)
-    st[W["state"] == 255] = -1
-    return dict(W, state=st)
-
-
-def check_oracle(P, o, V, C, tag):
-    """The planes of one replica against one oracle: test_gpu_parity.check_lists' per-vehicle assertions."""
-    L, veh = o.lists(), o.vehicles()
-    n, na = L["idle_off"][-1], L["arr_off"][-1]
-    idle = np.zeros(V, dtype=bool); idle[L["idle_veh"][:n]] = True
-    fly = L["arr_veh"][:na]
-    assert ((P["state"] == 0) == idle).all() and set(np.flatnonzero(P["state"] > 0)) == set(fly.tolist()), tag
-    assert n + na == V and (P["state"] >= 0).all(), tag
-    np.testing.assert_array_equal(P["node"][idle], veh["loc"][idle], err_msg=tag)
-    np.testing.assert_array_equal(P["node"][fly], veh["dest"][fly], err_msg=tag)
-    np.testing.assert_array_equal(P["order"][fly], veh["order"][fly], err_msg=tag)
-    np.testing.assert_array_equal(P["state"][fly], np.where(veh["order"][fly] >= 0, 1, 2), err_msg=tag)
-    np.testing.assert_array_equal(P["arrive_min"][fly], L["arr_min"][:na], err_msg=tag)
-    assert (P["arrive_min"][idle] == -1).all() and (P["order"][idle] == -1).all(), tag
-    cl_idle = np.empty(V, dtype=np.int64); cl_idle[L["idle_veh"][:n]] = np.repeat(np.arange(C), np.diff(L["idle_off"]))
-    np.testing.assert_array_equal(P["cluster"][idle], cl_idle[idle], err_msg=tag)
-    cl_fly = np.empty(V, dtype=np.int64); cl_fly[fly] = np.repeat(np.arange(C), np.diff(L["arr_off"]))
-    np.testing.assert_array_equal(P["cluster"][fly], cl_fly[fly], err_msg=tag)
-    if "source" in P:
-        assert ((P["source"] == 0) == idle).all() and (P["source"][fly] >= 1).all() and (P["source"][fly] <= 4).all(), tag
 
 
 def check_planes(env, oracles, tag, seen=None):

@@ -2787,8 +2787,8 @@ static int apply_dispatch_device_impl(vds_handle *h, int32_t K, const void *dev_
 static int apply_dispatch_vehicles_device_impl(vds_handle *h, const void *dev_targets) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: call vds_reset first");
     if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: must follow vds_step of the current tick (the hook runs after Match, :1083)");
+    if (h->S.V <= 0) return VDS_OK;          // (no vehicles: a [replicas][0] tensor has no address, and there is nothing to read from it)
     if (!dev_targets) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: the target tensor is null");
-    if (h->S.V <= 0) return VDS_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
     if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + h->S.V >= (1 << DENSE_ID_BITS))
