@@ -5,8 +5,13 @@ the poorest neighbouring cluster, when that neighbour is poorer than its own clu
 
     python examples/per_vehicle_policy.py [replicas]
 
+The learning signal of such a policy is what each vehicle earned: every slot the policy adds the ``value`` word of the per-vehicle
+outcome block (``vehicle_outcomes_torch``, ``run_hooked(vehicle_outcomes=True)``) into a running per-vehicle return ``[R, V]`` on the
+device, where the ``order`` word says the vehicle was matched.  Summed over the vehicles the day's return is the matched order value
+of ``counters_torch`` (word 3), which the example checks.
+
 The same day is run twice - slot by slot through the entry points, and as ONE ``run_hooked`` launch with the policy captured into the
-day graph - and both must end with the same counters."""
+day graph - and both must end with the same counters and the same returns."""
 import os
 import sys
 
@@ -20,8 +25,9 @@ from vehicles_dispatch_simulator_amd import workloads
 from vehicles_dispatch_simulator_amd._lib import COUNTER_NAMES
 
 
-def build_policy(env, w, targets):
-    """The policy as a function without arguments on the library's blocks (fixed addresses: capturable); writes `targets` [R, V]."""
+def build_policy(env, w, targets, returns):
+    """The policy as a function without arguments on the library's blocks (fixed addresses: capturable); writes `targets` [R, V] and
+    adds the slot's earnings into `returns` [R, V] (int64)."""
     R, V, C, N = env.R, env.V, env.C, w.city.N
     n2c, cost = w.city.node2cluster, np.asarray(w.city.cost)
     # nearest[c, n]: the node of cluster c with the smallest RoadCost(n, node) = cost[node, n] (simulator.py:263-264)
@@ -36,10 +42,12 @@ def build_policy(env, w, targets):
     nearest_t, nbr_t = torch.from_numpy(nearest).cuda().reshape(-1), torch.from_numpy(nbr).cuda()
     ob = env.obs_torch(inflight=False)                                   # [5, R, C]: idle_pre, idle_now, supply, cl_orders, inflight
     pl = env.vehicles_torch(state=True, node=True, cluster=True, arrive_min=False, order=False)
+    earned = env.vehicle_outcomes_torch()                                # [R, V, 4]: order, wait, value, pickup of the slot's match
     BIG = 1 << 30
     cidx = torch.arange(C, device="cuda")
 
     def policy():
+        returns.add_(torch.where(earned[..., 0] >= 0, earned[..., 2], torch.zeros_like(earned[..., 2])).to(torch.int64))
         surplus = (ob[1] + ob[2] - ob[3]).to(torch.int64)                 # [R, C]
         around = torch.where(nbr_t >= 0, surplus[:, nbr_t.clamp(min=0)], torch.full((R,) + tuple(nbr_t.shape), BIG, device="cuda"))   # [R, C, deg]
         best = around.argmin(dim=2)                                       # the poorest neighbour of every cluster
@@ -67,19 +75,22 @@ if __name__ == "__main__":
     env = w.make_env(R, stream=stream.cuda_stream, idle_cap=cap, ring_cap=cap, far_cap=cap)
     init = w.vehicle_nodes(R)
     targets = torch.full((R, env.V), -1, dtype=torch.int32, device="cuda")
+    returns = torch.zeros((R, env.V), dtype=torch.int64, device="cuda")
     env.reset(init)
-    policy = build_policy(env, w, targets)
+    policy = build_policy(env, w, targets, returns)
 
     # 1. slot by slot
     for t in range(env.T):
         env.step()
         env.obs_torch(inflight=False)
         env.vehicles_torch(state=True, node=True, cluster=True, arrive_min=False, order=False)
+        env.vehicle_outcomes_torch()
         policy()
         env.apply_dispatch_vehicles_torch(targets)
         env.advance()
     env.sync()
     stepwise = env.counters()
+    stepwise_returns = returns.clone()
 
     # 2. one launch: the policy captured, planes and targets as nodes of the day graph
     side = torch.cuda.Stream()
@@ -92,13 +103,21 @@ if __name__ == "__main__":
     with torch.cuda.graph(graph):
         policy()
     env.reset(init)
-    env.run_hooked(env.T, policy_graph=graph, inflight=False, vehicle_planes=dict(state=True, node=True, cluster=True), vehicle_targets=targets)
+    returns.zero_()
+    env.run_hooked(env.T, policy_graph=graph, inflight=False, vehicle_planes=dict(state=True, node=True, cluster=True), vehicle_targets=targets,
+                   vehicle_outcomes=True)
     env.sync()
     hooked = env.counters()
+    matched_value = env.counters_torch()[:, 3].clone()                   # matched OrderValue per replica
+    torch.cuda.synchronize()
+    earned_ok = bool(torch.equal(returns.sum(dim=1), matched_value)) and bool(torch.equal(returns, stepwise_returns))
+    total, best = int(returns.sum().item()), int(returns.max().item())
     env.close()
 
     print("slot by slot : " + counters_line(stepwise))
     print("one launch   : " + counters_line(hooked))
-    same = bool((stepwise == hooked).all())
+    print("per-vehicle return of the day: total %d (matched order value %d), best vehicle %d: %s" %
+          (total, int(matched_value.sum().item()), best, "the vehicles' returns add up to the counters" if earned_ok else "MISMATCH"))
+    same = bool((stepwise == hooked).all()) and earned_ok
     print("%d cities x %d slots, %d dispatches: both days end with %s counters" % (R, env.T, int(hooked[:, 4].sum()), "the SAME" if same else "DIFFERENT"))
     sys.exit(0 if same else 1)

@@ -428,6 +428,43 @@ int vds_read_vehicles_all(vds_handle *h, int32_t planes, int32_t *out);
  * `planes` outside 0 .. 63: VDS_EINVAL. */
 int vds_run_hooked_vehicles(vds_handle *h, int32_t planes, const void *dev_targets);
 
+/* What each vehicle earned in the slot stepped last - the per-vehicle counterpart of vds_outcomes_device: the order MatchFunction
+ * (:924-975, neighbour search :978-996 included) gave the vehicle in that slot.  One int32 block [R][V][4], replicas in the caller's
+ * order, indexed by vehicle number as vds_read_vehicles is; the four words of a vehicle sit next to each other:
+ *   0 order    Order.ID of the order the vehicle was matched with in that slot; -1: none
+ *   1 wait     that order's PickupWaitTime (:949, :952): the road cost from where the vehicle stood to the pickup node
+ *   2 value    that order's OrderValue (:341-342)
+ *   3 pickup   that order's pickup node, a global node id
+ * A vehicle without a match in that slot reads -1 in all four words: a consumer tests order >= 0.  A vehicle is matched at most once
+ * per slot (it leaves IdleVehicles at :963 and comes back only through a later UpdateFunction).  Rejected orders and the order that
+ * is never processed (quirk Q1, :914-915) touch no vehicle.  Which cluster served the order does not matter: after a neighbour-search
+ * match the vehicle's row shows the order, and `pickup` lies in another cluster than the one the vehicle idled in.  The slot's
+ * dispatch calls and vds_advance do not change the block.  "The slot stepped last" is the one vds_outcomes_device reports (after
+ * vds_run / vds_run_hooked: the last slot of the run); before the first step of an episode the block reads all -1, and so does a
+ * replica whose order day is over at that slot (vds_load_order_days; vds_outcomes_device reads zeros there).  After vds_restore
+ * replica r shows src_replica[r]'s rows of the snapshot's slot.  VDS_EINVAL before vds_reset.
+ * Sum checks: over the vehicles of a replica, the count of order >= 0 is plane 0 (served) of vds_outcomes_device summed over
+ * clusters; the sums of wait and value over those vehicles are planes 2 and 3 summed over clusters.
+ * Words of one vehicle are interleaved, unlike the [k][R][..] planes of the neighbouring blocks, on purpose: an access keyed by
+ * vehicle id is a memory line of its own, so a match costs one 16-byte store where four planes would cost four scattered stores.
+ * In torch word k is blk[..., k], a strided view.  There is no plane mask: the block is always written whole.
+ * vds_vehicle_outcomes_device computes the block asynchronously on the handle's stream and returns its device address (16-byte
+ * aligned): made on the first call, fixed until the tables are re-made (vds_load_orders* with other sizes, vds_set_idle_cap,
+ * vds_set_replica_days, vds_destroy).  With no vehicles (V == 0) the call launches nothing, returns VDS_OK and an address nobody
+ * may dereference.  No tick, vds_run or vds_run_hooked computes it unless vds_run_hooked_vehicle_outcomes switched it on.
+ * vds_read_vehicle_outcomes: the same, copied to the host (synchronous) and de-interleaved: each array [R*V] replica-major; any
+ * pointer may be NULL, every element of an array that is passed is written. */
+int vds_vehicle_outcomes_device(vds_handle *h, void **dev_ptr);
+int vds_read_vehicle_outcomes(vds_handle *h, int32_t *order, int32_t *wait, int32_t *value, int32_t *pickup);
+
+/* Sticky switch of vds_run_hooked, like vds_run_hooked_idle_heads: on != 0 - every slot of the calls that follow refreshes the block
+ * of vds_vehicle_outcomes_device (the -1 fill included) behind the slot's tick, observation, outcome, idle-head and vehicle-plane
+ * nodes and before the policy node, so a captured policy reads what each vehicle earned in the slot (get the address from
+ * vds_vehicle_outcomes_device before capturing: it is the one the day uses); 0 - off, the default: nothing is launched and
+ * vds_run_hooked builds node for node the graph it builds without this switch.  The day graph is keyed by the switch and by the
+ * block's address; with replica groups every group has its own nodes. */
+int vds_run_hooked_vehicle_outcomes(vds_handle *h, int32_t on);
+
 /* Snapshot and restore of the episode state, with per-replica forking (no reference counterpart: a Simulation cannot go back; the
  * nearest thing is Reload + replaying the day, simulator.py:130-212, :1048-1091).
  * vds_snapshot saves the episode state of every replica as it stands: the idle lists, the vehicles on their way (arrival ring, far
@@ -441,7 +478,7 @@ int vds_run_hooked_vehicles(vds_handle *h, int32_t planes, const void *dev_targe
  * one a vds_reset issues to regrow them), the first vds_supply_inplace, the whole-day change of k_tick_dense's base form.
  * vds_restore makes replica r (the caller's index) continue from the snapshot's replica src_replica[r] - [replicas] host values, not
  * retained; NULL: every replica from itself, the plain rollback.  Afterwards every read entry point (vds_read_obs and the device
- * planes, vds_read_counters, vds_read_orders, vds_read_lists, vds_read_vehicles, vds_read_vehicles_all, vds_read_outcomes, vds_read_idle_heads, vds_clock)
+ * planes, vds_read_counters, vds_read_orders, vds_read_lists, vds_read_vehicles, vds_read_vehicles_all, vds_read_outcomes, vds_read_vehicle_outcomes, vds_read_idle_heads, vds_clock)
  * answers as it did at the snapshot with replica r showing src_replica[r]'s values, and vds_step / vds_run / vds_run_hooked continue
  * from the restored slot.  Asynchronous.  A snapshot can be restored any number of times.  VDS_ESTATE "no snapshot" when there is
  * none or it is void; VDS_EINVAL for a map entry outside [0, replicas); VDS_EINVAL with order days per replica when replica r and

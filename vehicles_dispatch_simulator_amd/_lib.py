@@ -85,6 +85,9 @@ SYMBOLS = {
     "vds_run_hooked_idle_heads": (C.c_int, [_VP, _I32]),
     "vds_vehicles_device": (C.c_int, [_VP, _I32, C.POINTER(_VP)]),
     "vds_read_vehicles_all": (C.c_int, [_VP, _I32, _VP]),
+    "vds_vehicle_outcomes_device": (C.c_int, [_VP, C.POINTER(_VP)]),
+    "vds_read_vehicle_outcomes": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "vds_run_hooked_vehicle_outcomes": (C.c_int, [_VP, _I32]),
     "vds_snapshot": (C.c_int, [_VP]),
     "vds_restore": (C.c_int, [_VP, _VP]),
     "vds_restore_device": (C.c_int, [_VP, _VP]),

@@ -97,7 +97,7 @@ enum Mem {
     MEM_ORDERS,                          // tables of the loaded day (parked by the next vds_load_orders* for its own tables, DevGroup::recycle)
     MEM_MAP,                             // the replica -> day map's device arrays (replaced by vds_set_replica_days / the next load)
     MEM_RESULTS,                         // per-replica result tables out / arr / slog (sized by S.R)
-    MEM_STATE,                           // per-replica state (kept across days while the capacities still fit), with d_outc, d_heads and d_veh
+    MEM_STATE,                           // per-replica state (kept across days while the capacities still fit), with d_outc, d_heads, d_veh and d_vout
     MEM_IDLE,                            // the idle table alone (regrown by vds_reset / vds_set_idle_cap)
     MEM_SNAP,                            // the snapshot store
     MEM_GROUPS
@@ -227,6 +227,9 @@ struct vds_handle {
     int hooked_veh_planes = 0;               // vds_run_hooked_vehicles: every slot of vds_run_hooked refreshes these planes of d_veh (sticky; 0: none)
     const void *hooked_veh_targets = nullptr;    // ... and applies this per-vehicle target tensor behind the policy (sticky; null: off)
     int hook_veh_planes = 0; const void *hook_veh_targets = nullptr; const int *hook_veh = nullptr;   // ... and what the graph at hand was built with
+    int *d_vout = nullptr;                   // vds_vehicle_outcomes_device: int32 [R_ext][V][4], made on the first request (in MEM_STATE)
+    int hooked_vout = 0;                     // vds_run_hooked_vehicle_outcomes: every slot of vds_run_hooked refreshes d_vout (sticky; 0: off)
+    const int *hook_vout = nullptr;          // ... and what the graph at hand was built with (null: off)
     const void *hook_actions = nullptr;
     void *hook_policy = nullptr;
     hipStream_t hook_stream = nullptr;
@@ -783,6 +786,7 @@ static int alloc_state(vds_handle *h, int O) {
     h->d_outc = nullptr;                                 // (the outcome block lived there: made again on the next request)
     h->d_heads = nullptr; h->heads_L = 0;                // (and the idle-heads block)
     h->d_veh = nullptr;                                  // (and the per-vehicle planes)
+    h->d_vout = nullptr;                                 // (and the per-vehicle outcomes)
     S.idle_cap = idle_cap; S.fl_cap = far_cap; S.in_cap = far_cap; S.H = H; S.ring_cap = ring_cap;
     const size_t B = (size_t)C * R;
     h->alloc_dense = S.dense; h->alloc_st = S.dense_st;
@@ -1727,6 +1731,7 @@ int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger) {
 static int ensure_outcomes(vds_handle *h);
 static int ensure_idle_heads(vds_handle *h, int L);
 static int ensure_vehicles(vds_handle *h);
+static int ensure_vehicle_outcomes(vds_handle *h);
 
 static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
     if (policy_graph && h->hook_policy_inst != policy_graph) {
@@ -1741,6 +1746,7 @@ static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int3
         if ((planes & VDS_PLANE_OUTCOMES) && (rc = vds_outcomes_device(h, nullptr))) return rc;
         if (h->hooked_heads_L > 0 && (rc = vds_idle_heads_device(h, h->hooked_heads_L, nullptr))) return rc;
         if (h->hooked_veh_planes && (rc = vds_vehicles_device(h, h->hooked_veh_planes, nullptr))) return rc;
+        if (h->hooked_vout && (rc = vds_vehicle_outcomes_device(h, nullptr))) return rc;
         if (policy_graph) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
         if (K > 0 && dev_actions && (rc = vds_apply_dispatch_device(h, K, dev_actions))) return rc;
         if (h->hooked_veh_targets && (rc = vds_apply_dispatch_vehicles_device(h, h->hooked_veh_targets))) return rc;
@@ -1764,6 +1770,9 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     const int VP = h->S.V > 0 ? h->hooked_veh_planes : 0;
     const int *VT = h->S.V > 0 ? (const int *)h->hooked_veh_targets : nullptr;
     if (VP) { const int rcv = ensure_vehicles(h); if (rcv) return rcv; }
+    // per-vehicle outcomes of the hooked day (vds_run_hooked_vehicle_outcomes)
+    const bool VO = h->S.V > 0 && h->hooked_vout != 0;
+    if (VO) { const int rcv = ensure_vehicle_outcomes(h); if (rcv) return rcv; }
     if (VT && h->S.dense && (long long)K + h->S.V >= (1 << DENSE_ID_BITS))
         return fail(h, VDS_ECAPACITY, "vds_run_hooked: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
     const bool groupable = run_groups_hybrid(h) || run_groups_plain(h);
@@ -1778,7 +1787,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     const bool same = h->hook_exec && h->hook_gen == h->tables_gen && h->hook_t0 == h->t && h->hook_n == n_ticks && h->hook_G == G && h->hook_planes == planes && h->hook_K == K &&
                       h->hook_actions == dev_actions && h->hook_policy == policy_graph && h->hook_stream == h->stream && h->hook_outc == h->d_outc &&
                       h->hook_heads == (HL > 0 ? h->d_heads : nullptr) && h->hook_heads_L == HL &&
-                      h->hook_veh_planes == VP && h->hook_veh_targets == VT && h->hook_veh == (VP ? h->d_veh : nullptr);
+                      h->hook_veh_planes == VP && h->hook_veh_targets == VT && h->hook_veh == (VP ? h->d_veh : nullptr) &&
+                      h->hook_vout == (VO ? h->d_vout : nullptr);
     if (!same) {
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
@@ -1799,6 +1809,11 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                     c.add(emit_vehicle_fill, h->S, VP, h->d_veh, r.lo, r.n);
                     c.add(emit_vehicle_lists, h->S, h->D, t, VP, h->d_veh, r.lo, r.n);
                     if (vehicle_pull_needed(h->S, t)) c.add(emit_vehicle_pull, h->S, h->D, t, VP, h->d_veh, r.lo, r.n);
+                }
+                // what each vehicle of the group earned in the slot (vds_run_hooked_vehicle_outcomes): the -1 fill, then the scatter of the slot's orders
+                if (VO) {
+                    c.add(emit_vehicle_outcomes_fill, h->S, h->d_vout, r.lo, r.n);
+                    if (h->S.Oq > 0) c.add(emit_vehicle_outcomes, h->S, h->D, t, 1, h->d_vout, r.lo, r.n);
                 }
             }
             if (policy_graph) {
@@ -1824,12 +1839,14 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
         }
         const bool same_shape = h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) && (h->hook_heads_L > 0) == (HL > 0) &&
                                 (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr) &&
-                                (h->hook_veh_planes != 0) == (VP != 0) && (h->hook_veh_targets != nullptr) == (VT != nullptr);
+                                (h->hook_veh_planes != 0) == (VP != 0) && (h->hook_veh_targets != nullptr) == (VT != nullptr) &&
+                                (h->hook_vout != nullptr) == VO;
         if (!install_graph(h, drop_hook_graph, &h->hook_exec, h->hook_stream, same_shape, g)) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
         h->hook_t0 = h->t; h->hook_n = n_ticks; h->hook_G = G; h->hook_planes = planes; h->hook_K = K; h->hook_actions = dev_actions;
         h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen; h->hook_outc = h->d_outc;
         h->hook_heads = HL > 0 ? h->d_heads : nullptr; h->hook_heads_L = HL;
         h->hook_veh_planes = VP; h->hook_veh_targets = VT; h->hook_veh = VP ? h->d_veh : nullptr;
+        h->hook_vout = VO ? h->d_vout : nullptr;
     }
     HIPCHK(h, hipGraphLaunch(h->hook_exec, h->stream));
     h->t += n_ticks;
@@ -1880,7 +1897,7 @@ int vds_sync(vds_handle *h) {
 // replica map (vds_snapshot.hip).  What is saved: hdr, cnt, idle, ring, ring_min, ring_cnt, fl, both inbox parities, sup, arr, out and the
 // clock (t, last_stepped, the dispatch sequence numbers).  What is not: work / slog / dry (consumed or cleared inside the slot's own
 // launches), err / slow_tick / sup_slot (rewritten by every tick launch; the slot word is set to the restored slot's), the derived
-// blocks (d_obs, d_outc, d_heads, d_veh, d_cnt_*: not saved, refreshed on request after a restore) and stamp (every stamp is 0xFFFF between API calls: the lists are compact there).
+// blocks (d_obs, d_outc, d_heads, d_veh, d_vout, d_cnt_*: not saved, refreshed on request after a restore - d_vout from `out`, which is saved: replica r then shows the rows of src[r] at the snapshot's slot) and stamp (every stamp is 0xFFFF between API calls: the lists are compact there).
 static void snap_free(vds_handle *h) {
     vds_handle::Snap &s = h->snap;
     if (!h->mem[MEM_SNAP].empty()) (void)hipStreamSynchronize(h->stream);           // (a copy may still be running)
@@ -2336,6 +2353,60 @@ static int read_vehicles_all_impl(vds_handle *h, int32_t planes, int32_t *out) {
 
 int vds_read_vehicles_all(vds_handle *h, int32_t planes, int32_t *out) {
     return guarded(h, "vds_read_vehicles_all", [&] { return read_vehicles_all_impl(h, planes, out); });
+}
+
+// What each vehicle earned in the slot stepped last (MatchFunction's matches, :924-975): k_vehicle_outcomes_fill + k_vehicle_outcomes
+// (vds_vehicle_outcomes.hip) into the int32 [R_ext][V][4] block, made on the first request (it lives with the state tables: re-made
+// when they are).  Derived from `out` on request, like d_outc: nothing of it is kept between calls or saved in a snapshot.
+static int ensure_vehicle_outcomes(vds_handle *h) {
+    if (h->d_vout) return VDS_OK;
+    const size_t n = std::max<size_t>(4 * (size_t)h->R_ext * h->S.V, 4);
+    const int rc = dev_alloc(h, MEM_STATE, &h->d_vout, n);
+    if (rc) { h->d_vout = nullptr; return rc; }
+    return VDS_OK;          // (not cleared here: nobody sees the block before k_vehicle_outcomes_fill has written all of it)
+}
+
+static int vehicle_outcomes_device_impl(vds_handle *h, void **dev_ptr) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_vehicle_outcomes_device: call vds_reset first");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int rc = ensure_vehicle_outcomes(h);
+    if (rc) return rc;
+    // every element is written, whatever the memory held: the -1 fill of every replica's rows, then the scatter of the slot's orders
+    if ((size_t)h->R_ext * h->S.V > 0) launch_vehicle_outcomes(h->S, h->D, std::max(h->last_stepped, 0), h->last_stepped >= 0 ? 1 : 0, h->d_vout, h->stream);
+    HIPCHK(h, hipGetLastError());
+    if (dev_ptr) *dev_ptr = h->d_vout;
+    return VDS_OK;
+}
+
+int vds_vehicle_outcomes_device(vds_handle *h, void **dev_ptr) {
+    return guarded(h, "vds_vehicle_outcomes_device", [&] { return vehicle_outcomes_device_impl(h, dev_ptr); });
+}
+
+static int read_vehicle_outcomes_impl(vds_handle *h, int32_t *order, int32_t *wait, int32_t *value, int32_t *pickup) {
+    const int rc = vehicle_outcomes_device_impl(h, nullptr);
+    if (rc) return rc;
+    const size_t RV = (size_t)h->R_ext * h->S.V;
+    if (RV == 0) return vds_sync(h);
+    // one copy of the block, de-interleaved on the host
+    std::vector<int32_t> blk(4 * RV);
+    HIPCHK(h, hipMemcpyAsync(blk.data(), h->d_vout, 4 * RV * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    const int rcs = vds_sync(h);
+    if (rcs) return rcs;
+    int32_t *dst[4] = {order, wait, value, pickup};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k])
+            for (size_t i = 0; i < RV; ++i) dst[k][i] = blk[4 * i + k];
+    return VDS_OK;
+}
+
+int vds_read_vehicle_outcomes(vds_handle *h, int32_t *order, int32_t *wait, int32_t *value, int32_t *pickup) {
+    return guarded(h, "vds_read_vehicle_outcomes", [&] { return read_vehicle_outcomes_impl(h, order, wait, value, pickup); });
+}
+
+int vds_run_hooked_vehicle_outcomes(vds_handle *h, int32_t on) {
+    if (!h) return VDS_EINVAL;
+    h->hooked_vout = on ? 1 : 0;
+    return VDS_OK;
 }
 
 int vds_run_hooked_idle_heads(vds_handle *h, int32_t L) {

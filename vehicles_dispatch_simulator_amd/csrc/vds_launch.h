@@ -64,6 +64,12 @@ void emit_vehicle_lists(const Emit &e, const Static &S, const State &D, int t_la
 bool vehicle_pull_needed(const Static &S, int t_last);
 void emit_vehicle_pull(const Emit &e, const Static &S, const State &D, int t_last, int planes, int *out, int r_lo, int r_n);
 void launch_vehicle_planes(const Static &S, const State &D, int t_last, int planes, int *out, hipStream_t st);
+// ---- vds_vehicle_outcomes.hip
+// blk: int32 [R_ext][V][4] {order, wait, value, pickup} per vehicle (16-byte aligned); t: slot stepped last, stepped == 0: none since
+// the reset.  Two kernels, one launcher each (a graph node each): the -1 fill of the replicas' rows, then the scatter of the slot's orders
+void emit_vehicle_outcomes_fill(const Emit &e, const Static &S, int *blk, int r_lo, int r_n);
+void emit_vehicle_outcomes(const Emit &e, const Static &S, const State &D, int t, int stepped, int *blk, int r_lo, int r_n);
+void launch_vehicle_outcomes(const Static &S, const State &D, int t, int stepped, int *blk, hipStream_t st);
 // ---- vds_dispatch_vehicles.hip
 // targets: int32 [R_ext][V] target node per vehicle (negative: stay); seq_base: sequence numbers the slot's earlier dispatch calls used
 void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, int seq_base, int r_lo, int r_n);

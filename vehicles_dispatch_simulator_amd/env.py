@@ -16,6 +16,7 @@ PICKUP_REJECT_THRESHOLD = 600_000_000_000   # int(config/setting.py:7 PICKUPTIME
 PLANE_OUTCOMES = 32                         # vds_run_hooked plane bit of the per-cluster order outcomes (VDS_PLANE_OUTCOMES)
 OUTCOME_NAMES = ("served", "rejected", "wait_sum", "value_sum")
 VEHICLE_PLANE_NAMES = ("state", "node", "cluster", "arrive_min", "order", "source")      # planes of vds_vehicles_device, bit k = plane k
+VEHICLE_OUTCOME_NAMES = ("order", "wait", "value", "pickup")      # words of a vehicle's row in the block of vds_vehicle_outcomes_device
 
 
 def _p(a: Optional[np.ndarray]):
@@ -294,7 +295,7 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_run(self._h, int(n_ticks)))
 
     def run_hooked(self, n_ticks: int, actions=None, policy_graph=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False,
-                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None):
+                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None, vehicle_outcomes=False):
         """``n_ticks`` slots of ``SimCity`` WITH the dispatch hook on the device as one graph launch (``vds_run_hooked``): per slot
         step -> the named observation planes into the block ``obs_torch`` returns (``outcomes=True``: also the slot's per-cluster
         order outcomes into the block ``outcomes_torch`` returns; ``idle_heads=L``: also the first ``L`` entries of every idle list
@@ -308,7 +309,10 @@ class BatchedDispatchEnv:
         the policy against ``vehicles_torch(...)`` / ``vehicles_device_ptr(mask)`` taken before: the day uses that block.
         ``vehicle_targets``: the contiguous int32 CUDA tensor ``[R, V]`` the policy writes, applied every slot as
         ``apply_dispatch_vehicles_torch`` behind the policy and behind ``actions`` (``None``: off).  Both are switched off again by
-        a call without them."""
+        a call without them.
+        ``vehicle_outcomes=True`` (``vds_run_hooked_vehicle_outcomes``): every slot also refreshes, before the policy, the block
+        ``vehicle_outcomes_torch`` returns - what each vehicle earned in the slot.  Capture the policy against that tensor (or
+        ``vehicle_outcomes_device_ptr()``) taken before: the day uses that block.  Off again by a call without it."""
         planes = (1 if idle_pre else 0) | (2 if idle_now else 0) | (4 if supply else 0) | (8 if cl_orders else 0) | (16 if inflight else 0)
         planes |= PLANE_OUTCOMES if outcomes else 0
         K, ptr = 0, None
@@ -324,6 +328,7 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_run_hooked_idle_heads(self._h, int(idle_heads)))
         vt = None if vehicle_targets is None else self._vehicle_targets_ptr(vehicle_targets, "run_hooked")
         self._chk(self._lib.vds_run_hooked_vehicles(self._h, self._vehicle_mask(vehicle_planes), vt))
+        self._chk(self._lib.vds_run_hooked_vehicle_outcomes(self._h, 1 if vehicle_outcomes else 0))
         self._chk(self._lib.vds_run_hooked(self._h, int(n_ticks), planes, K, ptr, C.c_void_p(raw) if raw is not None else None))
 
     def run_hooked_invalidate(self):
@@ -611,6 +616,40 @@ class BatchedDispatchEnv:
         out = np.empty((len(ks), self.R, self.V), dtype=np.int32)
         self._chk(self._lib.vds_read_vehicles_all(self._h, sum(1 << k for k in ks), _p(out)))
         return {VEHICLE_PLANE_NAMES[k]: out[i] for i, k in enumerate(ks)}
+
+    def vehicle_outcomes_device_ptr(self) -> int:
+        """Device pointer of the int32 ``[R][V][4]`` block of per-vehicle order outcomes, computed for the slot stepped last
+        (``vds_vehicle_outcomes_device``); fixed until the state tables are re-made.  With ``V == 0`` nobody may dereference it."""
+        p = C.c_void_p()
+        self._chk(self._lib.vds_vehicle_outcomes_device(self._h, C.byref(p)))
+        return p.value
+
+    def vehicle_outcomes_torch(self):
+        """What each vehicle earned in the slot stepped last, as a zero-copy ``torch`` int32 tensor ``[R, V, 4]`` on the GPU: the
+        words of ``VEHICLE_OUTCOME_NAMES`` - ``order`` (``Order.ID`` of the order ``MatchFunction`` gave the vehicle in that slot,
+        ``-1``: none), ``wait`` (its ``PickupWaitTime``), ``value`` (its ``OrderValue``), ``pickup`` (its pickup node, a global node
+        id).  A vehicle without a match reads ``-1`` in all four: test ``blk[..., 0] >= 0``.  Word ``k`` is the strided view
+        ``blk[..., k]`` (a vehicle's words share one 16-byte piece, so that a match is one store).  Asynchronous on the handle's
+        stream; aliases library memory, overwritten by the next call or by ``run_hooked(vehicle_outcomes=True)``."""
+        import torch
+
+        ptr = self.vehicle_outcomes_device_ptr()
+        if self.R * self.V == 0:
+            return torch.empty((self.R, self.V, 4), dtype=torch.int32, device=torch.device("cuda", self.device))
+
+        class _Block:
+            pass
+
+        blk = _Block()
+        blk.__cuda_array_interface__ = {"shape": (self.R, self.V, 4), "typestr": "<i4", "data": (ptr, False), "version": 2, "strides": None}
+        return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+
+    def vehicle_outcomes(self) -> Dict[str, np.ndarray]:
+        """``vehicle_outcomes_torch`` copied to the host and de-interleaved (``vds_read_vehicle_outcomes``, synchronous):
+        ``{order, wait, value, pickup}``, each int32 ``[R, V]``."""
+        arrs = [np.empty((self.R, self.V), dtype=np.int32) for _ in VEHICLE_OUTCOME_NAMES]
+        self._chk(self._lib.vds_read_vehicle_outcomes(self._h, *[_p(a) for a in arrs]))
+        return dict(zip(VEHICLE_OUTCOME_NAMES, arrs))
 
     def work(self) -> Dict[str, int]:
         out = np.zeros(8, dtype=np.int64)
