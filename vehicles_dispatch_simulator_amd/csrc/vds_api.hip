@@ -293,6 +293,14 @@ static int upload(vds_handle *h, Mem g, T **p, const std::vector<T, A> &v) {
     return VDS_OK;
 }
 
+// plane i (n elements each) of the device block `blk` to dst[i], for the k planes whose dst[i] is not null; then vds_sync
+template <typename T>
+static int read_planes(vds_handle *h, const T *blk, size_t n, void *const *dst, int k) {
+    for (int i = 0; i < k; ++i)
+        if (dst[i]) HIPCHK(h, hipMemcpyAsync(dst[i], blk + i * n, n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    return vds_sync(h);
+}
+
 // What a change makes stale.  DAY_GRAPHS / GRAPH_TABLES: the day graphs hold other launches / the tables or capacities they read changed
 // (run_stale and tables_gen, which the hooked day graph and the reset image compare); STATE_MEANING: the state / result tables were re-made
 // or mean something else (state_gen: a snapshot taken before is void).  The first two move the same fields today, on purpose: the call
@@ -2150,11 +2158,8 @@ int vds_obs_inplace(vds_handle *h, int32_t plane, void **dev_ptr, int64_t *strid
 static int read_obs_impl(vds_handle *h, int32_t *idle_pre, int32_t *idle_now, int32_t *supply, int32_t *cl_orders, int32_t *inflight) {
     int rc = vds_obs_device(h, nullptr);
     if (rc) return rc;
-    const size_t RC = (size_t)h->R_ext * h->S.C;
-    int32_t *dst[5] = {idle_pre, idle_now, supply, cl_orders, inflight};
-    for (int k = 0; k < 5; ++k)
-        if (dst[k]) HIPCHK(h, hipMemcpyAsync(dst[k], h->d_obs + k * RC, RC * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return vds_sync(h);
+    void *dst[5] = {idle_pre, idle_now, supply, cl_orders, inflight};
+    return read_planes(h, h->d_obs, (size_t)h->R_ext * h->S.C, dst, 5);
 }
 
 // value of the orders of replica r's day that have not been processed (yet): they count in SumOrderValue (:1095-1100)
@@ -2245,11 +2250,8 @@ int vds_outcomes_device(vds_handle *h, void **dev_ptr) {
 static int read_outcomes_impl(vds_handle *h, int64_t *served, int64_t *rejected, int64_t *wait_sum, int64_t *value_sum) {
     const int rc = outcomes_device_impl(h, nullptr);
     if (rc) return rc;
-    const size_t RC = (size_t)h->R_ext * h->S.C;
-    int64_t *dst[4] = {served, rejected, wait_sum, value_sum};
-    for (int k = 0; k < 4; ++k)
-        if (dst[k]) HIPCHK(h, hipMemcpyAsync(dst[k], h->d_outc + k * RC, RC * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    return vds_sync(h);
+    void *dst[4] = {served, rejected, wait_sum, value_sum};
+    return read_planes(h, h->d_outc, (size_t)h->R_ext * h->S.C, dst, 4);
 }
 
 int vds_read_outcomes(vds_handle *h, int64_t *served, int64_t *rejected, int64_t *wait_sum, int64_t *value_sum) {
@@ -2293,11 +2295,8 @@ int vds_idle_heads_device(vds_handle *h, int32_t L, void **dev_ptr) {
 static int read_idle_heads_impl(vds_handle *h, int32_t L, int32_t *veh, int32_t *node) {
     const int rc = idle_heads_device_impl(h, L, nullptr);
     if (rc) return rc;
-    const size_t RCL = (size_t)h->R_ext * h->S.C * L;
-    int32_t *dst[2] = {veh, node};
-    for (int k = 0; k < 2; ++k)
-        if (dst[k]) HIPCHK(h, hipMemcpyAsync(dst[k], h->d_heads + k * RCL, RCL * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return vds_sync(h);
+    void *dst[2] = {veh, node};
+    return read_planes(h, h->d_heads, (size_t)h->R_ext * h->S.C * L, dst, 2);
 }
 
 int vds_read_idle_heads(vds_handle *h, int32_t L, int32_t *veh, int32_t *node) {
@@ -2389,8 +2388,8 @@ static int read_vehicle_outcomes_impl(vds_handle *h, int32_t *order, int32_t *wa
     if (RV == 0) return vds_sync(h);
     // one copy of the block, de-interleaved on the host
     std::vector<int32_t> blk(4 * RV);
-    HIPCHK(h, hipMemcpyAsync(blk.data(), h->d_vout, 4 * RV * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    const int rcs = vds_sync(h);
+    void *all[1] = {blk.data()};
+    const int rcs = read_planes(h, h->d_vout, 4 * RV, all, 1);
     if (rcs) return rcs;
     int32_t *dst[4] = {order, wait, value, pickup};
     for (int k = 0; k < 4; ++k)
