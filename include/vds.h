@@ -465,6 +465,77 @@ int vds_read_vehicle_outcomes(vds_handle *h, int32_t *order, int32_t *wait, int3
  * block's address; with replica groups every group has its own nodes. */
 int vds_run_hooked_vehicle_outcomes(vds_handle *h, int32_t on);
 
+/* The idle roster: every idle vehicle of every replica in the order a DispatchFunction meets them,
+ *     for cluster in self.Clusters:                 # ascending cluster id
+ *         for vehicle in cluster.IdleVehicles:      # list order
+ * (:893-898) - the idle group of vds_read_lists (idle_off, idle_veh, idle_node) for ALL replicas at once, as one device block:
+ *   planes  int32 [3][R][V], replicas in the caller's order, indexed by roster position i
+ *             0 veh      Vehicle.ID
+ *             1 node     LocationNode as a global node id
+ *             2 cluster  the cluster whose IdleVehicles holds the vehicle
+ *   off     int32 [R][C + 1]: off[r][c] is the roster position of the head of Clusters[c].IdleVehicles, off[r][C] the number of idle
+ *           vehicles of replica r.
+ * Entry i = off[r][c] + p describes list position p of cluster c - the idle_pos of vds_apply_dispatch*.  All three planes hold -1
+ * from off[r][C] on.  Every element of the block is written by every refresh, whatever the memory held (the block is not cleared when
+ * it is made).  A replica whose order day is over reports its standing lists (as vds_idle_heads_device does).  With V == 0 the planes
+ * have no elements and off is all zero.  Unlike vds_idle_heads_device there is no cap on the length of a list, and unlike the planes
+ * of vds_vehicles_device nothing is keyed by vehicle id: the refresh's stores and a policy's reads are contiguous runs.
+ * vds_idle_roster_device refreshes the block asynchronously on the handle's stream (one kernel) and returns the addresses of the planes
+ * and of the offsets (either pointer may be NULL): ONE allocation, made on the first call, fixed until the tables are re-made
+ * (vds_load_orders* with other sizes, vds_set_idle_cap, vds_set_replica_days, vds_destroy); not part of a snapshot - after
+ * vds_restore a refresh shows replica r with the lists of src_replica[r].  No tick, vds_run or vds_run_hooked computes it unless
+ * vds_run_hooked_roster switched it on.  VDS_EINVAL before vds_reset; VDS_ECAPACITY with more than 16000 clusters (the kernel keeps a
+ * replica's offsets in LDS).
+ * vds_read_idle_roster: the same, copied to the host (synchronous): veh / node / cluster [R*V], off [R*(C+1)]; any pointer may be
+ * NULL.
+ * Out of scope: the Simulation shell does not use the roster. */
+int vds_idle_roster_device(vds_handle *h, void **dev_planes, void **dev_off);
+int vds_read_idle_roster(vds_handle *h, int32_t *veh, int32_t *node, int32_t *cluster, int32_t *off);
+
+/* Dispatch by roster position: dev_targets is a device-resident int32 tensor [replicas][V]; entry [r][i] belongs to roster entry i of
+ * replica r as the LAST refresh of the idle roster showed it.  One call is this DispatchFunction body (:893-898) in every replica r:
+ *     i = 0
+ *     for cluster in self.Clusters:                     # ascending cluster id
+ *         for vehicle in cluster.IdleVehicles[:]:       # list order, as the roster shows it
+ *             n = dev_targets[r][i];  i += 1
+ *             if n >= 0:
+ *                 cluster.IdleVehicles.remove(vehicle)    # order of the others preserved
+ *                 Clusters[NodeID2Cluster[n]].VehiclesArrivetime[vehicle] = RealExpTime + RoadCost(vehicle.LocationNode, n)
+ *                 vehicle.DeliveryPoint = n;  self.DispatchNum += 1;  self.TotallyDispatchCost += cost
+ *   - Dict insertion order among the call's entries is ROSTER order - cluster, then list position - not vehicle number: arrival
+ *     dicts differ from those of vds_apply_dispatch_vehicles_device given the same moves, and equal those of vds_apply_dispatch with
+ *     one action per mover in roster order.  The arrival key's id is the slot's sequence base + i.
+ *   - Entries of earlier dispatch calls of the same slot (any form) come before; order-carrying entries are ordered as they are for
+ *     the other forms.
+ *   - A negative entry means stay.  There is no cap on the moves of a call.  Entries at or beyond off[r][C] are never looked at.
+ *   - Refused and skipped as in the vehicle form - the vehicle stays, nothing of it is posted, the other moves are applied, the sticky
+ *     dispatch error is reported once by the next vds_sync / vds_read_* (VDS_ESTATE): a target >= N; a target node in no cluster;
+ *     any non-negative target in a replica whose order day is over.
+ *   - Capacity overflows (ring_cap, far_cap) stay what they are: VDS_ECAPACITY, sticky.
+ * Freshness.  The tensor only means something against the lists the roster described, so the handle keeps a flag: set by
+ * vds_idle_roster_device (and vds_read_idle_roster), cleared by every call that can change an idle list or re-make the tables -
+ * vds_step, vds_run, vds_run_hooked, every dispatch form including this one, every vds_reset*, vds_restore*, vds_load_*,
+ * vds_set_replica_days, vds_set_idle_cap.  With the flag clear the call returns VDS_ESTATE and applies nothing: refresh, write the
+ * targets, call.  Behind the flag the kernel checks every (cluster, replica) list against the offsets it reads targets by: a list
+ * whose length is not off[r][c + 1] - off[r][c] (the offsets were overwritten) applies nothing and raises the sticky dispatch error.
+ * Must follow vds_step of the current slot and precede vds_advance (VDS_EINVAL otherwise, and for a NULL tensor - except with V == 0,
+ * where the call is a no-op and dev_targets is not looked at).  Asynchronous on the handle's stream, which must be ordered after the
+ * producer of the tensor.  A call uses up V dispatch sequence numbers of the slot; on the dense layout VDS_ECAPACITY when the slot's
+ * calls would pass 2^25 of them.  Out of scope: a per-entry arrive_min / counted as in vds_apply_dispatch_ex. */
+int vds_apply_dispatch_roster_device(vds_handle *h, const void *dev_targets);
+
+/* Sticky switch of vds_run_hooked, like vds_run_hooked_vehicles: the idle roster and targets by roster position inside the hooked day.
+ *   on           != 0: every slot of the calls that follow refreshes the block of vds_idle_roster_device (one kernel node per replica
+ *                group) behind the slot's tick, observation, outcome, idle-head, vehicle-plane and vehicle-outcome nodes and before
+ *                the policy node (get the addresses from vds_idle_roster_device before capturing: they are the ones the day uses);
+ *   dev_targets  int32 [replicas][V] (NULL - off, the default): applied every slot as vds_apply_dispatch_roster_device behind the
+ *                policy node, with sequence numbers from 0; a slot uses up V of them.  Needs on != 0 (VDS_EINVAL otherwise).
+ * A day with roster targets takes no other dispatch form: vds_run_hooked returns VDS_EINVAL with K > 0 or with the per-vehicle
+ * targets of vds_run_hooked_vehicles - an earlier dispatch of the slot would change the lists the positions refer to.
+ * The day graph is keyed by the switch and by the addresses of the block and of the targets.  Never called, or (0, NULL):
+ * vds_run_hooked builds node for node the graph it builds without this switch. */
+int vds_run_hooked_roster(vds_handle *h, int32_t on, const void *dev_targets);
+
 /* Snapshot and restore of the episode state, with per-replica forking (no reference counterpart: a Simulation cannot go back; the
  * nearest thing is Reload + replaying the day, simulator.py:130-212, :1048-1091).
  * vds_snapshot saves the episode state of every replica as it stands: the idle lists, the vehicles on their way (arrival ring, far

@@ -88,6 +88,10 @@ SYMBOLS = {
     "vds_vehicle_outcomes_device": (C.c_int, [_VP, C.POINTER(_VP)]),
     "vds_read_vehicle_outcomes": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "vds_run_hooked_vehicle_outcomes": (C.c_int, [_VP, _I32]),
+    "vds_idle_roster_device": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP)]),
+    "vds_read_idle_roster": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "vds_apply_dispatch_roster_device": (C.c_int, [_VP, _VP]),
+    "vds_run_hooked_roster": (C.c_int, [_VP, _I32, _VP]),
     "vds_snapshot": (C.c_int, [_VP]),
     "vds_restore": (C.c_int, [_VP, _VP]),
     "vds_restore_device": (C.c_int, [_VP, _VP]),

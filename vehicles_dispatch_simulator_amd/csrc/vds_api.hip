@@ -97,7 +97,7 @@ enum Mem {
     MEM_ORDERS,                          // tables of the loaded day (parked by the next vds_load_orders* for its own tables, DevGroup::recycle)
     MEM_MAP,                             // the replica -> day map's device arrays (replaced by vds_set_replica_days / the next load)
     MEM_RESULTS,                         // per-replica result tables out / arr / slog (sized by S.R)
-    MEM_STATE,                           // per-replica state (kept across days while the capacities still fit), with d_outc, d_heads, d_veh and d_vout
+    MEM_STATE,                           // per-replica state (kept across days while the capacities still fit), with d_outc, d_heads, d_veh, d_vout and d_roster
     MEM_IDLE,                            // the idle table alone (regrown by vds_reset / vds_set_idle_cap)
     MEM_SNAP,                            // the snapshot store
     MEM_GROUPS
@@ -230,6 +230,11 @@ struct vds_handle {
     int *d_vout = nullptr;                   // vds_vehicle_outcomes_device: int32 [R_ext][V][4], made on the first request (in MEM_STATE)
     int hooked_vout = 0;                     // vds_run_hooked_vehicle_outcomes: every slot of vds_run_hooked refreshes d_vout (sticky; 0: off)
     const int *hook_vout = nullptr;          // ... and what the graph at hand was built with (null: off)
+    int *d_roster = nullptr;                 // vds_idle_roster_device: int32 [3][R_ext][V] planes, then int32 [R_ext][C + 1] offsets, made on the first request (in MEM_STATE)
+    bool roster_fresh = false;               // the block describes the idle lists as they stand: set by a refresh, cleared by whatever can change a list or re-make the tables
+    int hooked_roster = 0;                   // vds_run_hooked_roster: every slot of vds_run_hooked refreshes d_roster (sticky; 0: off)
+    const void *hooked_roster_targets = nullptr;     // ... and applies this target tensor by roster position behind the policy (sticky; null: off)
+    const int *hook_roster = nullptr; const void *hook_roster_targets = nullptr;    // ... and what the graph at hand was built with
     const void *hook_actions = nullptr;
     void *hook_policy = nullptr;
     hipStream_t hook_stream = nullptr;
@@ -309,9 +314,10 @@ enum Changed : unsigned { DAY_GRAPHS = 1, GRAPH_TABLES = 2, STATE_MEANING = 4 };
 static void invalidate(vds_handle *h, unsigned changed) {
     if (changed & (DAY_GRAPHS | GRAPH_TABLES)) { h->run_stale = true; h->tables_gen++; }
     if (changed & STATE_MEANING) h->state_gen++;
+    h->roster_fresh = false;
 }
 // the episode clock back to the start of the day
-static void clock_reset(vds_handle *h) { h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1; }
+static void clock_reset(vds_handle *h) { h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1; h->roster_fresh = false; }
 
 // No C++ exception may cross the C ABI (vds.h: "never abort"): host allocation failures and the like become a
 // status code + vds_last_error.
@@ -795,6 +801,7 @@ static int alloc_state(vds_handle *h, int O) {
     h->d_heads = nullptr; h->heads_L = 0;                // (and the idle-heads block)
     h->d_veh = nullptr;                                  // (and the per-vehicle planes)
     h->d_vout = nullptr;                                 // (and the per-vehicle outcomes)
+    h->d_roster = nullptr; h->roster_fresh = false;      // (and the idle roster)
     S.idle_cap = idle_cap; S.fl_cap = far_cap; S.in_cap = far_cap; S.H = H; S.ring_cap = ring_cap;
     const size_t B = (size_t)C * R;
     h->alloc_dense = S.dense; h->alloc_st = S.dense_st;
@@ -1571,6 +1578,7 @@ static int step_impl(vds_handle *h, bool flush = true) {
     if (h->last_stepped == h->t) return fail(h, VDS_EINVAL, "vds_step: tick %d already stepped; call vds_advance", h->t);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (h->t >= h->S.T) return fail(h, VDS_EINVAL, "vds_step: tick %d is past the end of the day (%d ticks, :1048)", h->t, h->S.T);
+    h->roster_fresh = false;
     const bool hybrid = run_groups_hybrid(h), replica2 = h->dfs_mode && !hybrid && h->dfs2_ok && h->cfg.force_generic != 1;
     hipEvent_t a = nullptr, b = nullptr;
     if (h->profiling && (!h->dfs_mode || hybrid || replica2)) {
@@ -1681,6 +1689,7 @@ static int build_group_graph(vds_handle *h, int32_t n_ticks, int G, hipGraph_t *
 // tick over all replicas.
 int vds_run(vds_handle *h, int32_t n_ticks) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_run: call vds_reset first");
+    h->roster_fresh = false;
     if (!run_graph_on(h) || h->profiling || n_ticks < 8 || h->last_stepped == h->t || h->t + n_ticks > h->S.T) return run_eager(h, n_ticks);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     { const int rcs = dev_copy_sync(h); if (rcs) return rcs; }
@@ -1740,6 +1749,8 @@ static int ensure_outcomes(vds_handle *h);
 static int ensure_idle_heads(vds_handle *h, int L);
 static int ensure_vehicles(vds_handle *h);
 static int ensure_vehicle_outcomes(vds_handle *h);
+static int ensure_idle_roster(vds_handle *h);
+static int *roster_off(vds_handle *h);
 
 static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
     if (policy_graph && h->hook_policy_inst != policy_graph) {
@@ -1755,9 +1766,11 @@ static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int3
         if (h->hooked_heads_L > 0 && (rc = vds_idle_heads_device(h, h->hooked_heads_L, nullptr))) return rc;
         if (h->hooked_veh_planes && (rc = vds_vehicles_device(h, h->hooked_veh_planes, nullptr))) return rc;
         if (h->hooked_vout && (rc = vds_vehicle_outcomes_device(h, nullptr))) return rc;
+        if (h->hooked_roster && (rc = vds_idle_roster_device(h, nullptr, nullptr))) return rc;
         if (policy_graph) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
         if (K > 0 && dev_actions && (rc = vds_apply_dispatch_device(h, K, dev_actions))) return rc;
         if (h->hooked_veh_targets && (rc = vds_apply_dispatch_vehicles_device(h, h->hooked_veh_targets))) return rc;
+        if (h->hooked_roster_targets && (rc = vds_apply_dispatch_roster_device(h, h->hooked_roster_targets))) return rc;
         if ((rc = vds_advance(h))) return rc;
     }
     return VDS_OK;
@@ -1769,7 +1782,11 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
         return fail(h, VDS_EINVAL, "vds_run_hooked: planes is a mask of the five observation planes and VDS_PLANE_OUTCOMES (0 .. 63), K in [0, 64] with a non-null action tensor");
     if (h->last_stepped == h->t) return fail(h, VDS_EINVAL, "vds_run_hooked: tick %d already stepped; call vds_advance", h->t);
     if (h->t + n_ticks > h->S.T) return fail(h, VDS_EINVAL, "vds_run_hooked: %d slots from slot %d on run past the end of the day (%d slots, :1048)", n_ticks, h->t, h->S.T);
+    // roster targets are positions in the lists as the refresh saw them: an earlier dispatch of the slot would change those lists
+    if (h->hooked_roster_targets && (K > 0 || h->hooked_veh_targets))
+        return fail(h, VDS_EINVAL, "vds_run_hooked: roster targets (vds_run_hooked_roster) cannot share a day with K > 0 actions or per-vehicle targets: an earlier dispatch of the slot changes the lists the roster positions refer to");
     if (n_ticks == 0) return VDS_OK;
+    h->roster_fresh = false;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (planes & VDS_PLANE_OUTCOMES) { const int rco = ensure_outcomes(h); if (rco) return rco; }
     const int HL = h->hooked_heads_L;
@@ -1781,6 +1798,12 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     // per-vehicle outcomes of the hooked day (vds_run_hooked_vehicle_outcomes)
     const bool VO = h->S.V > 0 && h->hooked_vout != 0;
     if (VO) { const int rcv = ensure_vehicle_outcomes(h); if (rcv) return rcv; }
+    // idle roster / targets by roster position of the hooked day (vds_run_hooked_roster)
+    const bool RO = h->hooked_roster != 0;
+    const int *RT = h->S.V > 0 ? (const int *)h->hooked_roster_targets : nullptr;
+    if (RO) { const int rcr = ensure_idle_roster(h); if (rcr) return rcr; }
+    if (RT && h->S.dense && h->S.V >= (1 << DENSE_ID_BITS))
+        return fail(h, VDS_ECAPACITY, "vds_run_hooked: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
     if (VT && h->S.dense && (long long)K + h->S.V >= (1 << DENSE_ID_BITS))
         return fail(h, VDS_ECAPACITY, "vds_run_hooked: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
     const bool groupable = run_groups_hybrid(h) || run_groups_plain(h);
@@ -1796,7 +1819,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                       h->hook_actions == dev_actions && h->hook_policy == policy_graph && h->hook_stream == h->stream && h->hook_outc == h->d_outc &&
                       h->hook_heads == (HL > 0 ? h->d_heads : nullptr) && h->hook_heads_L == HL &&
                       h->hook_veh_planes == VP && h->hook_veh_targets == VT && h->hook_veh == (VP ? h->d_veh : nullptr) &&
-                      h->hook_vout == (VO ? h->d_vout : nullptr);
+                      h->hook_vout == (VO ? h->d_vout : nullptr) &&
+                      h->hook_roster == (RO ? h->d_roster : nullptr) && h->hook_roster_targets == RT;
     if (!same) {
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
@@ -1823,6 +1847,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                     c.add(emit_vehicle_outcomes_fill, h->S, h->d_vout, r.lo, r.n);
                     if (h->S.Oq > 0) c.add(emit_vehicle_outcomes, h->S, h->D, t, 1, h->d_vout, r.lo, r.n);
                 }
+                // the group's idle roster as the tick left the lists (vds_run_hooked_roster): one kernel writes every element
+                if (RO) c.add(emit_idle_roster, h->S, h->D, h->d_roster, roster_off(h), r.lo, r.n);
             }
             if (policy_graph) {
                 // (the child graph between two EMPTY nodes: with several parents / several children attached to the child-graph node
@@ -1839,6 +1865,10 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                 const Rows r = group_rows(h, gi, G);
                 if (r.n > 0) c.add(emit_dispatch_vehicles, h->S, h->D, t, VT, K, r.lo, r.n);
             }
+            for (int gi = 0; gi < G && RT; ++gi) {
+                const Rows r = group_rows(h, gi, G);
+                if (r.n > 0) c.add(emit_dispatch_roster, h->S, h->D, t, RT, roster_off(h), 0, r.lo, r.n);
+            }
         }
         if (c.err != hipSuccess) {
             (void)hipGraphDestroy(g);
@@ -1848,23 +1878,27 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
         const bool same_shape = h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) && (h->hook_heads_L > 0) == (HL > 0) &&
                                 (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr) &&
                                 (h->hook_veh_planes != 0) == (VP != 0) && (h->hook_veh_targets != nullptr) == (VT != nullptr) &&
-                                (h->hook_vout != nullptr) == VO;
+                                (h->hook_vout != nullptr) == VO &&
+                                (h->hook_roster != nullptr) == RO && (h->hook_roster_targets != nullptr) == (RT != nullptr);
         if (!install_graph(h, drop_hook_graph, &h->hook_exec, h->hook_stream, same_shape, g)) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
         h->hook_t0 = h->t; h->hook_n = n_ticks; h->hook_G = G; h->hook_planes = planes; h->hook_K = K; h->hook_actions = dev_actions;
         h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen; h->hook_outc = h->d_outc;
         h->hook_heads = HL > 0 ? h->d_heads : nullptr; h->hook_heads_L = HL;
         h->hook_veh_planes = VP; h->hook_veh_targets = VT; h->hook_veh = VP ? h->d_veh : nullptr;
         h->hook_vout = VO ? h->d_vout : nullptr;
+        h->hook_roster = RO ? h->d_roster : nullptr; h->hook_roster_targets = RT;
     }
     HIPCHK(h, hipGraphLaunch(h->hook_exec, h->stream));
     h->t += n_ticks;
     h->last_stepped = h->t - 1;
-    if (K > 0 || VT) { h->dispatch_seq += (K + (VT ? h->S.V : 0)) * n_ticks; h->seq_tick = -1; }
+    if (K > 0 || VT || RT) { h->dispatch_seq += (K + (VT || RT ? h->S.V : 0)) * n_ticks; h->seq_tick = -1; }
     return VDS_OK;
 }
 
 int vds_run_hooked(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
-    return guarded(h, "vds_run_hooked", [&] { return run_hooked_impl(h, n_ticks, planes, K, dev_actions, policy_graph); });
+    const int rc = guarded(h, "vds_run_hooked", [&] { return run_hooked_impl(h, n_ticks, planes, K, dev_actions, policy_graph); });
+    if (h) h->roster_fresh = false;          // (the day's own refreshes were for its own dispatch nodes)
+    return rc;
 }
 
 int vds_run_hooked_invalidate(vds_handle *h) {
@@ -1993,6 +2027,7 @@ static int restore_finish(vds_handle *h, const int *user_dev_map, const int *map
     if (rc) return rc;
     h->t = s.t; h->last_stepped = s.last_stepped; h->dispatch_seq = s.dispatch_seq; h->seq_tick0 = s.seq_tick0; h->seq_tick = s.seq_tick;
     h->restored_episode = true;
+    h->roster_fresh = false;
     return VDS_OK;
 }
 static int restore_check(vds_handle *h, const char *who) {
@@ -2073,6 +2108,7 @@ static int apply_dispatch_impl(vds_handle *h, int32_t n, const int32_t *replica,
     if (n == 0) return VDS_OK;
     if (n < 0 || !replica || !from_cluster || !idle_pos || !target_node) return fail(h, VDS_EINVAL, "vds_apply_dispatch: bad argument");
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->roster_fresh = false;
     const Static &S = h->S;
     if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
     if (S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + n >= (1 << DENSE_ID_BITS))
@@ -2400,6 +2436,58 @@ static int read_vehicle_outcomes_impl(vds_handle *h, int32_t *order, int32_t *wa
 
 int vds_read_vehicle_outcomes(vds_handle *h, int32_t *order, int32_t *wait, int32_t *value, int32_t *pickup) {
     return guarded(h, "vds_read_vehicle_outcomes", [&] { return read_vehicle_outcomes_impl(h, order, wait, value, pickup); });
+}
+
+// Every idle vehicle of every replica in DispatchFunction's order (`for cluster in self.Clusters: for vehicle in cluster.IdleVehicles`,
+// :893-898) - the idle group of read_lists_impl for all replicas: k_idle_roster (vds_idle_roster.hip) into the int32 [3][R_ext][V]
+// planes and the int32 [R_ext][C + 1] offsets behind them, ONE block made on the first request (it lives with the state tables:
+// re-made when they are).  Derived on request: nothing of it is saved in a snapshot.
+static int *roster_off(vds_handle *h) { return h->d_roster + 3 * (size_t)h->R_ext * h->S.V; }
+static int ensure_idle_roster(vds_handle *h) {
+    if (h->d_roster) return VDS_OK;
+    if (h->S.C > IDLE_ROSTER_C_MAX) return fail(h, VDS_ECAPACITY, "vds_idle_roster_device: %d clusters; k_idle_roster keeps a replica's offsets in LDS, at most %d", h->S.C, (int)IDLE_ROSTER_C_MAX);
+    const size_t n = 3 * (size_t)h->R_ext * h->S.V + (size_t)h->R_ext * (h->S.C + 1);
+    const int rc = dev_alloc(h, MEM_STATE, &h->d_roster, n);
+    if (rc) { h->d_roster = nullptr; return rc; }
+    return VDS_OK;          // (not cleared here: nobody sees the block before k_idle_roster has written all of it)
+}
+
+static int idle_roster_device_impl(vds_handle *h, void **dev_planes, void **dev_off) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_idle_roster_device: call vds_reset first");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int rc = ensure_idle_roster(h);
+    if (rc) return rc;
+    launch_idle_roster(h->S, h->D, h->d_roster, roster_off(h), h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->roster_fresh = true;
+    if (dev_planes) *dev_planes = h->d_roster;
+    if (dev_off) *dev_off = roster_off(h);
+    return VDS_OK;
+}
+
+int vds_idle_roster_device(vds_handle *h, void **dev_planes, void **dev_off) {
+    return guarded(h, "vds_idle_roster_device", [&] { return idle_roster_device_impl(h, dev_planes, dev_off); });
+}
+
+static int read_idle_roster_impl(vds_handle *h, int32_t *veh, int32_t *node, int32_t *cluster, int32_t *off) {
+    const int rc = idle_roster_device_impl(h, nullptr, nullptr);
+    if (rc) return rc;
+    void *dst[3] = {veh, node, cluster}, *dsto[1] = {off};
+    const size_t RV = (size_t)h->R_ext * h->S.V;
+    if (RV > 0) { const int rcp = read_planes(h, h->d_roster, RV, dst, 3); if (rcp) return rcp; }
+    return read_planes(h, roster_off(h), (size_t)h->R_ext * (h->S.C + 1), dsto, 1);
+}
+
+int vds_read_idle_roster(vds_handle *h, int32_t *veh, int32_t *node, int32_t *cluster, int32_t *off) {
+    return guarded(h, "vds_read_idle_roster", [&] { return read_idle_roster_impl(h, veh, node, cluster, off); });
+}
+
+int vds_run_hooked_roster(vds_handle *h, int32_t on, const void *dev_targets) {
+    if (!h) return VDS_EINVAL;
+    if (!on && dev_targets) return fail(h, VDS_EINVAL, "vds_run_hooked_roster: roster targets need the roster refreshed in every slot (on != 0)");
+    h->hooked_roster = on ? 1 : 0;
+    h->hooked_roster_targets = dev_targets;
+    return VDS_OK;
 }
 
 int vds_run_hooked_vehicle_outcomes(vds_handle *h, int32_t on) {
@@ -2843,6 +2931,7 @@ static int apply_dispatch_device_impl(vds_handle *h, int32_t K, const void *dev_
     if (K == 0) return VDS_OK;
     if (K < 0 || K > 64 || !dev_actions) return fail(h, VDS_EINVAL, "vds_apply_dispatch_device: K must be in [0, 64] and the action tensor non-null");
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->roster_fresh = false;
     if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
     if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + K >= (1 << DENSE_ID_BITS))
         return fail(h, VDS_ECAPACITY, "vds_apply_dispatch_device: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
@@ -2860,10 +2949,32 @@ static int apply_dispatch_vehicles_device_impl(vds_handle *h, const void *dev_ta
     if (h->S.V <= 0) return VDS_OK;          // (no vehicles: a [replicas][0] tensor has no address, and there is nothing to read from it)
     if (!dev_targets) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: the target tensor is null");
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->roster_fresh = false;
     if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
     if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + h->S.V >= (1 << DENSE_ID_BITS))
         return fail(h, VDS_ECAPACITY, "vds_apply_dispatch_vehicles_device: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
     launch_dispatch_vehicles(h->S, h->D, h->t, (const int *)dev_targets, h->dispatch_seq - h->seq_tick0, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->dispatch_seq += h->S.V;
+    return VDS_OK;
+}
+
+// The DispatchFunction body from one target node per ROSTER entry (k_dispatch_roster, vds_idle_roster.hip): sequence number of an
+// entry = the numbers the slot's earlier calls used + its roster position; the call uses up V of them.  The tensor only means
+// something against the lists the block describes: refused unless the block was refreshed since the last call that can change one.
+static int apply_dispatch_roster_device_impl(vds_handle *h, const void *dev_targets) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_apply_dispatch_roster_device: call vds_reset first");
+    if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_apply_dispatch_roster_device: must follow vds_step of the current tick (the hook runs after Match, :1083)");
+    if (h->S.V <= 0) return VDS_OK;          // (no vehicles: a [replicas][0] tensor has no address, and there is nothing to read from it)
+    if (!dev_targets) return fail(h, VDS_EINVAL, "vds_apply_dispatch_roster_device: the target tensor is null");
+    if (!h->roster_fresh || !h->d_roster)
+        return fail(h, VDS_ESTATE, "vds_apply_dispatch_roster_device: the idle roster is stale - the idle lists may have changed since it was refreshed (a step, a dispatch call, a reset, a restore); call vds_idle_roster_device and write the targets against that roster");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
+    if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + h->S.V >= (1 << DENSE_ID_BITS))
+        return fail(h, VDS_ECAPACITY, "vds_apply_dispatch_roster_device: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
+    h->roster_fresh = false;
+    launch_dispatch_roster(h->S, h->D, h->t, (const int *)dev_targets, roster_off(h), h->dispatch_seq - h->seq_tick0, h->stream);
     HIPCHK(h, hipGetLastError());
     h->dispatch_seq += h->S.V;
     return VDS_OK;
@@ -3000,6 +3111,10 @@ int vds_apply_dispatch_device(vds_handle *h, int32_t K, const void *dev_actions)
 
 int vds_apply_dispatch_vehicles_device(vds_handle *h, const void *dev_targets) {
     return guarded(h, "vds_apply_dispatch_vehicles_device", [&] { return apply_dispatch_vehicles_device_impl(h, dev_targets); });
+}
+
+int vds_apply_dispatch_roster_device(vds_handle *h, const void *dev_targets) {
+    return guarded(h, "vds_apply_dispatch_roster_device", [&] { return apply_dispatch_roster_device_impl(h, dev_targets); });
 }
 
 }  // extern "C"

@@ -74,6 +74,15 @@ void launch_vehicle_outcomes(const Static &S, const State &D, int t, int stepped
 // targets: int32 [R_ext][V] target node per vehicle (negative: stay); seq_base: sequence numbers the slot's earlier dispatch calls used
 void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, int seq_base, int r_lo, int r_n);
 void launch_dispatch_vehicles(const Static &S, const State &D, int t, const int *targets, int seq_base, hipStream_t st);
+// ---- vds_idle_roster.hip
+// planes: int32 [3][R_ext][V] {veh, node, cluster} by roster position, off: int32 [R_ext][C + 1]; one kernel writes every element of both
+// (dynamic LDS: idle_roster_lds, (C + 1) ints - C <= IDLE_ROSTER_C_MAX)
+enum { IDLE_ROSTER_C_MAX = 16000 };
+void emit_idle_roster(const Emit &e, const Static &S, const State &D, int *planes, int *off, int r_lo, int r_n);
+void launch_idle_roster(const Static &S, const State &D, int *planes, int *off, hipStream_t st);
+// targets: int32 [R_ext][V] target node per roster entry (negative: stay), against the offsets `off` of the refresh it was written for
+void emit_dispatch_roster(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *off, int seq_base, int r_lo, int r_n);
+void launch_dispatch_roster(const Static &S, const State &D, int t, const int *targets, const int *off, int seq_base, hipStream_t st);
 // ---- vds_snapshot.hip
 // the tables of a snapshot, one launch each: `src` -> `dst` are State views of the live tables and of the store (either way round),
 // map [S.R] stored replica -> stored source replica (null: identity), tdone the slots whose orders have been processed (SNAP_OUT)

@@ -17,6 +17,7 @@ PLANE_OUTCOMES = 32                         # vds_run_hooked plane bit of the pe
 OUTCOME_NAMES = ("served", "rejected", "wait_sum", "value_sum")
 VEHICLE_PLANE_NAMES = ("state", "node", "cluster", "arrive_min", "order", "source")      # planes of vds_vehicles_device, bit k = plane k
 VEHICLE_OUTCOME_NAMES = ("order", "wait", "value", "pickup")      # words of a vehicle's row in the block of vds_vehicle_outcomes_device
+IDLE_ROSTER_NAMES = ("veh", "node", "cluster")                   # planes of the block of vds_idle_roster_device
 
 
 def _p(a: Optional[np.ndarray]):
@@ -40,6 +41,8 @@ class BatchedDispatchEnv:
     Parameters mirror ``config/setting.py``: ``vehicles`` = VehiclesNumber, ``tick_minutes`` =
     TIMESTEP, ``neighbor_can_server`` = NeighborCanServer, ``depth_limit`` =
     NeighborServerDeepLimit (``simulator.py:290``)."""
+
+    _hooked_roster = False           # run_hooked(roster=True) switched vds_run_hooked_roster on: the next call without it switches it off
 
     def __init__(self, cost, node2cluster, nbr_off, nbr_idx, *, replicas: int, vehicles: int,
                  depth_limit: int = 0, neighbor_can_server: bool = False, tick_minutes: int = 10,
@@ -247,6 +250,17 @@ class BatchedDispatchEnv:
         that stream - as for ``apply_dispatch_torch``."""
         self._chk(self._lib.vds_apply_dispatch_vehicles_device(self._h, self._vehicle_targets_ptr(targets, "apply_dispatch_vehicles_torch")))
 
+    def apply_dispatch_roster_torch(self, targets):
+        """Dispatch by roster position (``vds_apply_dispatch_roster_device``): ``targets`` is a contiguous int32 CUDA tensor ``[R, V]`` on
+        the handle's device, ``targets[r, i]`` the node roster entry ``i`` of replica ``r`` goes to (negative: stays) - the answer of a
+        policy written on ``idle_roster_torch``.  Movers leave in roster order, cluster then list position
+        (``oracle.dispatch(ids_in_roster_order, targets)``); entries at or beyond ``off[r, C]`` are never read.  The roster must be
+        fresh: refreshed (``idle_roster_torch`` / ``idle_roster``) since the last ``step``, dispatch call, reset or restore - otherwise
+        the call raises and applies nothing.  A target ``>= N``, a target node in no cluster or a target in a replica whose order day is
+        over is skipped and raises once at the next ``sync`` / read.  Asynchronous, no host copy; the tensor must stay alive until the
+        handle's stream has passed the call and must have been produced on (or synchronised with) that stream."""
+        self._chk(self._lib.vds_apply_dispatch_roster_device(self._h, self._vehicle_targets_ptr(targets, "apply_dispatch_roster_torch")))
+
     def advance(self):
         self._chk(self._lib.vds_advance(self._h))
 
@@ -295,7 +309,7 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_run(self._h, int(n_ticks)))
 
     def run_hooked(self, n_ticks: int, actions=None, policy_graph=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False,
-                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None, vehicle_outcomes=False):
+                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None, vehicle_outcomes=False, roster=False, roster_targets=None):
         """``n_ticks`` slots of ``SimCity`` WITH the dispatch hook on the device as one graph launch (``vds_run_hooked``): per slot
         step -> the named observation planes into the block ``obs_torch`` returns (``outcomes=True``: also the slot's per-cluster
         order outcomes into the block ``outcomes_torch`` returns; ``idle_heads=L``: also the first ``L`` entries of every idle list
@@ -312,7 +326,12 @@ class BatchedDispatchEnv:
         a call without them.
         ``vehicle_outcomes=True`` (``vds_run_hooked_vehicle_outcomes``): every slot also refreshes, before the policy, the block
         ``vehicle_outcomes_torch`` returns - what each vehicle earned in the slot.  Capture the policy against that tensor (or
-        ``vehicle_outcomes_device_ptr()``) taken before: the day uses that block.  Off again by a call without it."""
+        ``vehicle_outcomes_device_ptr()``) taken before: the day uses that block.  Off again by a call without it.
+        ``roster=True`` (``vds_run_hooked_roster``): every slot also refreshes, before the policy, the idle roster
+        ``idle_roster_torch`` returns - capture the policy against those tensors taken before.  ``roster_targets``: the contiguous
+        int32 CUDA tensor ``[R, V]`` the policy writes by roster position, applied every slot as ``apply_dispatch_roster_torch``
+        behind the policy (``None``: off); it needs ``roster=True`` and excludes ``actions`` and ``vehicle_targets`` - an earlier
+        dispatch of the slot would change the lists the positions refer to.  Both off again by a call without them."""
         planes = (1 if idle_pre else 0) | (2 if idle_now else 0) | (4 if supply else 0) | (8 if cl_orders else 0) | (16 if inflight else 0)
         planes |= PLANE_OUTCOMES if outcomes else 0
         K, ptr = 0, None
@@ -322,6 +341,7 @@ class BatchedDispatchEnv:
             if str(actions.dtype) != "torch.int32" or not actions.is_cuda or not actions.is_contiguous():
                 raise Exception("run_hooked: expected a contiguous int32 CUDA tensor")
             K, ptr = int(actions.shape[1]), C.c_void_p(actions.data_ptr())
+        rt = None if roster_targets is None else self._vehicle_targets_ptr(roster_targets, "run_hooked")
         raw = None
         if policy_graph is not None:
             raw = policy_graph if isinstance(policy_graph, int) else int(policy_graph.raw_cuda_graph())
@@ -329,6 +349,10 @@ class BatchedDispatchEnv:
         vt = None if vehicle_targets is None else self._vehicle_targets_ptr(vehicle_targets, "run_hooked")
         self._chk(self._lib.vds_run_hooked_vehicles(self._h, self._vehicle_mask(vehicle_planes), vt))
         self._chk(self._lib.vds_run_hooked_vehicle_outcomes(self._h, 1 if vehicle_outcomes else 0))
+        if roster or roster_targets is not None or self._hooked_roster:
+            # (the switch is only touched by a day that uses it, or to switch it off again)
+            self._chk(self._lib.vds_run_hooked_roster(self._h, 1 if roster else 0, rt))
+            self._hooked_roster = bool(roster)
         self._chk(self._lib.vds_run_hooked(self._h, int(n_ticks), planes, K, ptr, C.c_void_p(raw) if raw is not None else None))
 
     def run_hooked_invalidate(self):
@@ -650,6 +674,52 @@ class BatchedDispatchEnv:
         arrs = [np.empty((self.R, self.V), dtype=np.int32) for _ in VEHICLE_OUTCOME_NAMES]
         self._chk(self._lib.vds_read_vehicle_outcomes(self._h, *[_p(a) for a in arrs]))
         return dict(zip(VEHICLE_OUTCOME_NAMES, arrs))
+
+    def idle_roster_device_ptr(self):
+        """Device pointers ``(planes, off)`` of the idle roster (``vds_idle_roster_device``), refreshed from the lists as they stand:
+        ``planes`` int32 ``[3][R][V]`` (``IDLE_ROSTER_NAMES``), ``off`` int32 ``[R][C + 1]`` - one allocation, fixed until the state
+        tables are re-made.  With ``V == 0`` nobody may dereference ``planes``."""
+        p, o = C.c_void_p(), C.c_void_p()
+        self._chk(self._lib.vds_idle_roster_device(self._h, C.byref(p), C.byref(o)))
+        return p.value, o.value
+
+    def idle_roster_torch(self):
+        """Every idle vehicle of every replica in ``DispatchFunction``'s order - ``for cluster in self.Clusters: for vehicle in
+        cluster.IdleVehicles`` - as zero-copy ``torch`` int32 views on the GPU: ``veh`` (``Vehicle.ID``), ``node`` (``LocationNode``,
+        a global node id) and ``cluster`` as ``[R, V]`` by roster position, ``off`` as ``[R, C + 1]`` (``off[r, c]``: position of the
+        head of cluster ``c``'s list, ``off[r, C]``: idle vehicles of replica ``r``).  Entry ``off[r, c] + p`` is list position ``p``
+        of cluster ``c``; the planes hold ``-1`` from ``off[r, C]`` on.  ``lists(r)``'s idle group for all replicas at once.
+        Asynchronous on the handle's stream; aliases library memory, overwritten by the next roster call or by
+        ``run_hooked(roster=True)``."""
+        import torch
+
+        pp, po = self.idle_roster_device_ptr()
+        dev = torch.device("cuda", self.device)
+
+        class _Block:
+            pass
+
+        bo = _Block()
+        bo.__cuda_array_interface__ = {"shape": (self.R, self.C + 1), "typestr": "<i4", "data": (po, False), "version": 2, "strides": None}
+        out = {"off": torch.as_tensor(bo, device=dev)}
+        if self.R * self.V == 0:
+            out.update({k: torch.empty((self.R, self.V), dtype=torch.int32, device=dev) for k in IDLE_ROSTER_NAMES})
+            return out
+        bp = _Block()
+        bp.__cuda_array_interface__ = {"shape": (3, self.R, self.V), "typestr": "<i4", "data": (pp, False), "version": 2, "strides": None}
+        t = torch.as_tensor(bp, device=dev)
+        out.update({k: t[i] for i, k in enumerate(IDLE_ROSTER_NAMES)})
+        return out
+
+    def idle_roster(self) -> Dict[str, np.ndarray]:
+        """``idle_roster_torch`` copied to the host (``vds_read_idle_roster``, synchronous): ``veh`` / ``node`` / ``cluster`` int32
+        ``[R, V]``, ``off`` int32 ``[R, C + 1]``."""
+        arrs = [np.empty((self.R, self.V), dtype=np.int32) for _ in IDLE_ROSTER_NAMES]
+        off = np.empty((self.R, self.C + 1), dtype=np.int32)
+        self._chk(self._lib.vds_read_idle_roster(self._h, *[_p(a) for a in arrs], _p(off)))
+        out = dict(zip(IDLE_ROSTER_NAMES, arrs))
+        out["off"] = off
+        return out
 
     def work(self) -> Dict[str, int]:
         out = np.zeros(8, dtype=np.int64)
