@@ -965,6 +965,86 @@ def test_a_replica_without_idle_vehicles():
     assert stats["empty"] >= 1 and stats["moved"] > 0, stats
 
 
+# ---- 9b. one walk, two forms --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kw", [{}, {"force_generic": 5}], ids=["dense", "wide"])
+def test_the_two_tensor_forms_differ_in_addressing_only(kw):
+    """k_dispatch_vehicles and k_dispatch_roster are one walk that differs in where a list position finds its target and its
+    sequence id.  With every vehicle in ONE list in ascending vehicle number, roster position == list position == vehicle number: one
+    target tensor means the same in both forms, down to the arrival keys - two environments built alike, one call of either form,
+    equal bit for bit from then on.  3 clusters, 2 replicas, 70 vehicles in the last cluster: two chunks, the second partial."""
+    C, V, R = 3, 70, 2
+    g = synth_fixture(C, V)
+    n2c, N = g["node2cluster"], int(g["N"])
+    last = int(np.flatnonzero(np.bincount(n2c[n2c >= 0], minlength=C) > 0)[-1])
+    # slot 0 and the slots behind it take no vehicle off the list: one order elsewhere opens the day, the others come an hour later
+    rel = g["o_release_min"]
+    first = int(np.flatnonzero(n2c[g["o_pickup"]] != last)[0])
+    keep = rel >= rel[first] + 60
+    keep[first] = True
+    keep[:first] = False
+    for k in ("o_release_min", "o_pickup", "o_delivery"):
+        g[k] = g[k][keep]
+    init = one_cluster_init(g, R, last)
+    caps = dict(idle_cap=128, ring_cap=256, far_cap=256)
+    envs = {form: make_env(g, R, **{**caps, **kw, **torch_stream_kw()}) for form in ("vehicle", "roster")}
+    for env in envs.values():
+        assert int(env.layout()["dense"]) == (0 if kw else 1)
+        env.reset(init)
+        env.step()
+    blk = envs["roster"].idle_roster_torch()
+    envs["roster"].sync()
+    ro = {k: v.cpu().numpy() for k, v in blk.items()}
+    for r in range(R):          # roster order and vehicle-number order agree
+        assert ro["off"][r].tolist() == [0] * (last + 1) + [V] * (C - last)
+        np.testing.assert_array_equal(ro["veh"][r], np.arange(V))
+    valid = np.flatnonzero(n2c >= 0)
+    movers = [0, 5, 31, 62, 63, 64, 65, 69]
+    tg = np.full((R, V), -1, dtype=np.int32)
+    for r in range(R):
+        tg[r, movers] = valid[(np.arange(len(movers)) * 5 + 3 * r) % valid.size]
+    tg[1, [1, 68]] = valid[[7 % valid.size, 11 % valid.size]]      # (the replicas differ)
+    tg[0, 40] = N + 3                                              # refused: a target >= N
+    envs["vehicle"].apply_dispatch_vehicles_torch(to_dev(tg))
+    envs["roster"].apply_dispatch_roster_torch(to_dev(tg))
+
+    def same(tag):
+        a, b = envs["vehicle"], envs["roster"]
+        for r in range(R):
+            for what, x, y in (("lists", a.lists(r), b.lists(r)), ("vehicles", a.vehicles(r), b.vehicles(r))):
+                assert set(x) == set(y)
+                for k in x:
+                    np.testing.assert_array_equal(x[k], y[k], err_msg="%s replica %d %s %s" % (tag, r, what, k))
+        np.testing.assert_array_equal(a.counters(), b.counters(), err_msg=tag)
+        return a.lists(0), a.lists(1)
+
+    for env in envs.values():       # the sticky dispatch error, in both: seen once
+        with pytest.raises(Exception, match="dispatch"):
+            env.sync()
+        env.sync()
+    L = same("behind the call")
+    cn = envs["vehicle"].counters()
+    assert cn[0, 4] == len(movers) and cn[1, 4] == len(movers) + 2
+    for r in range(R):
+        gone = set(np.flatnonzero(tg[r] >= 0).tolist()) - {40}
+        assert L[r]["idle_veh"][:L[r]["idle_off"][-1]].tolist() == [v for v in range(V) if v not in gone]      # survivors keep their order
+        assert set(L[r]["arr_veh"][:L[r]["arr_off"][-1]].tolist()) == gone
+    # ... and on until every mover has arrived: they enter the lists in the same order
+    on_the_way = lambda: sum(int((envs["vehicle"].vehicles(r)["state"] == 2).sum()) for r in range(R))
+    assert on_the_way() == 2 * len(movers) + 2
+    for t in range(1, envs["vehicle"].T):
+        for env in envs.values():
+            env.advance()
+            env.step()
+        same("slot %d" % t)
+        if on_the_way() == 0:
+            break
+    assert on_the_way() == 0, "the movers have not arrived by the end of the day"
+    for env in envs.values():
+        env.advance()
+        env.sync()
+        env.close()
+
+
 # ---- 10. written in full, whatever the memory held (the LAST tests of the module: a child that ends by a signal or at its limit
 # stops the ones behind it, and nothing of this module may start on the GPU behind such a child) ----------------------------------------------------------------------------------------
 # seconds of the selection under the product library on an MI355X, pytest start-up included; the limit follows as in

@@ -448,6 +448,39 @@ struct Chain {
     void add_child(hipGraph_t child) { add([child](const Emit &e) { *e.err = hipGraphAddChildGraphNode(e.node, e.graph, e.deps, e.ndeps, child); }); }
 };
 
+// A derived block of n elements, made on the first request (it lives with the state tables, MEM_STATE: re-made when they are).  fill:
+// the byte every element holds until the first refresh; negative: none - nobody sees the block before a kernel has written all of it.
+template <typename T>
+static int ensure_block(vds_handle *h, T **p, size_t n, int fill) {
+    if (*p) return VDS_OK;
+    const int rc = dev_alloc(h, MEM_STATE, p, n);
+    if (rc) { *p = nullptr; return rc; }
+    if (fill >= 0) HIPCHK(h, hipMemsetAsync(*p, fill, n * sizeof(T), h->stream));
+    return VDS_OK;
+}
+
+// What the three device dispatch entry points (`fn`) share, around the checks of their own arguments (`args`: VDS_OK or the
+// refusal): callable at all, nothing to do (n == 0, before the arguments are looked at), then the slot's sequence bookkeeping for the n
+// sequence numbers the call uses up.  *seq_base: the numbers the slot's earlier calls used; -1 with VDS_OK: nothing to do.  Whatever
+// is applied changes the lists: the roster is stale from here on.
+template <typename F>
+static int dispatch_begin(vds_handle *h, const char *fn, int n, F args, int *seq_base) {
+    *seq_base = -1;
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "%s: call vds_reset first", fn);
+    if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "%s: must follow vds_step of the current tick (the hook runs after Match, :1083)", fn);
+    if (n == 0) return VDS_OK;
+    const int rca = args();
+    if (rca) return rca;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
+    if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + n >= (1 << DENSE_ID_BITS))
+        return fail(h, VDS_ECAPACITY, "%s: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", fn, DENSE_ID_BITS, DENSE_ID_BITS);
+    h->roster_fresh = false;
+    *seq_base = h->dispatch_seq - h->seq_tick0;
+    h->dispatch_seq += n;
+    return VDS_OK;
+}
+
 // lanes per replica of k_tick_dense unless VDS_DENSE_LPR / vds_debug_dense say otherwise
 #ifndef DENSE_LPR_DEFAULT
 #define DENSE_LPR_DEFAULT 8
@@ -1745,12 +1778,28 @@ int vds_set_run_groups(vds_handle *h, int32_t groups, int32_t stagger) {
 // one submission per call instead of three or four launches per slot.  Like vds_run's it is one chain of nodes; replica groups (on
 // request only, see below) are launches of that chain, and the policy node, which sees all replicas, comes behind the last group's
 // planes and before the first group's dispatch.
-static int ensure_outcomes(vds_handle *h);
 static int ensure_idle_heads(vds_handle *h, int L);
-static int ensure_vehicles(vds_handle *h);
-static int ensure_vehicle_outcomes(vds_handle *h);
 static int ensure_idle_roster(vds_handle *h);
 static int *roster_off(vds_handle *h);
+
+static int ensure_outcomes(vds_handle *h) { return ensure_block(h, &h->d_outc, 4 * (size_t)h->R_ext * h->S.C, 0); }
+// (-1: "in neither container" until a plane's first refresh)
+static int ensure_vehicles(vds_handle *h) { return ensure_block(h, &h->d_veh, std::max<size_t>(6 * (size_t)h->R_ext * h->S.V, 1), 0xFF); }
+static int ensure_vehicle_outcomes(vds_handle *h) { return ensure_block(h, &h->d_vout, std::max<size_t>(4 * (size_t)h->R_ext * h->S.V, 4), -1); }
+
+// The two derived blocks that take more than one kernel, for the replicas [r_lo, r_lo + r_n) (r_n <= 0: all), on a stream or as
+// nodes of a day graph.  Every element of a requested plane / of the block is written, whatever the memory held: -1 first, then the scatter.
+// Per-vehicle planes `planes` of d_veh as slot t_last left them (-1: none stepped since the reset)
+static void refresh_vehicles(Chain &c, vds_handle *h, int t_last, int planes, int r_lo, int r_n) {
+    c.add(emit_vehicle_fill, h->S, planes, h->d_veh, r_lo, r_n);
+    c.add(emit_vehicle_lists, h->S, h->D, t_last, planes, h->d_veh, r_lo, r_n);
+    if (vehicle_pull_needed(h->S, t_last)) c.add(emit_vehicle_pull, h->S, h->D, t_last, planes, h->d_veh, r_lo, r_n);
+}
+// What each vehicle earned in slot t (stepped == 0: none stepped since the reset, the fill stands), d_vout
+static void refresh_vehicle_outcomes(Chain &c, vds_handle *h, int t, int stepped, int r_lo, int r_n) {
+    c.add(emit_vehicle_outcomes_fill, h->S, h->d_vout, r_lo, r_n);
+    if (stepped && h->S.Oq > 0) c.add(emit_vehicle_outcomes, h->S, h->D, t, stepped, h->d_vout, r_lo, r_n);
+}
 
 static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
     if (policy_graph && h->hook_policy_inst != policy_graph) {
@@ -1836,17 +1885,10 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                 if (planes & VDS_PLANE_OUTCOMES) c.add(emit_slot_outcomes, h->S, h->D, t, 1, h->d_outc, r.lo, r.n);
                 // the heads of the group's idle lists as the tick left them (vds_run_hooked_idle_heads)
                 if (HL > 0) c.add(emit_idle_heads, h->S, h->D, HL, h->d_heads, r.lo, r.n);
-                // the group's per-vehicle planes as the tick left them (vds_run_hooked_vehicles): the -1 fill as a kernel node, then the scatter
-                if (VP) {
-                    c.add(emit_vehicle_fill, h->S, VP, h->d_veh, r.lo, r.n);
-                    c.add(emit_vehicle_lists, h->S, h->D, t, VP, h->d_veh, r.lo, r.n);
-                    if (vehicle_pull_needed(h->S, t)) c.add(emit_vehicle_pull, h->S, h->D, t, VP, h->d_veh, r.lo, r.n);
-                }
-                // what each vehicle of the group earned in the slot (vds_run_hooked_vehicle_outcomes): the -1 fill, then the scatter of the slot's orders
-                if (VO) {
-                    c.add(emit_vehicle_outcomes_fill, h->S, h->d_vout, r.lo, r.n);
-                    if (h->S.Oq > 0) c.add(emit_vehicle_outcomes, h->S, h->D, t, 1, h->d_vout, r.lo, r.n);
-                }
+                // the group's per-vehicle planes as the tick left them (vds_run_hooked_vehicles)
+                if (VP) refresh_vehicles(c, h, t, VP, r.lo, r.n);
+                // what each vehicle of the group earned in the slot (vds_run_hooked_vehicle_outcomes)
+                if (VO) refresh_vehicle_outcomes(c, h, t, 1, r.lo, r.n);
                 // the group's idle roster as the tick left the lists (vds_run_hooked_roster): one kernel writes every element
                 if (RO) c.add(emit_idle_roster, h->S, h->D, h->d_roster, roster_off(h), r.lo, r.n);
             }
@@ -2258,22 +2300,13 @@ int vds_counters_device(vds_handle *h, void **dev_ptr) {
 
 // Per-cluster order outcomes of the slot stepped last (RewardFunction's view of Cluster.Orders, :999-1004): k_slot_outcomes into the
 // int64 [4][R_ext][C] block, made on the first request (it lives with the state tables: re-made when they are).
-static int ensure_outcomes(vds_handle *h) {
-    if (h->d_outc) return VDS_OK;
-    const size_t n = 4 * (size_t)h->R_ext * h->S.C;
-    const int rc = dev_alloc(h, MEM_STATE, &h->d_outc, n);
-    if (rc) { h->d_outc = nullptr; return rc; }
-    HIPCHK(h, hipMemsetAsync(h->d_outc, 0, n * sizeof(long long), h->stream));
-    return VDS_OK;
-}
-
 static int outcomes_device_impl(vds_handle *h, void **dev_ptr) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_outcomes_device: call vds_reset first");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int rc = ensure_outcomes(h);
     if (rc) return rc;
     if (h->last_stepped < 0) HIPCHK(h, hipMemsetAsync(h->d_outc, 0, 4 * (size_t)h->R_ext * h->S.C * sizeof(long long), h->stream));
-    else launch_slot_outcomes(h->S, h->D, h->last_stepped, 1, h->d_outc, h->stream);
+    else Chain(h->stream).add(emit_slot_outcomes, h->S, h->D, h->last_stepped, 1, h->d_outc, 0, 0);
     HIPCHK(h, hipGetLastError());
     if (dev_ptr) *dev_ptr = h->d_outc;
     return VDS_OK;
@@ -2304,12 +2337,9 @@ static int ensure_idle_heads(vds_handle *h, int L) {
         h->mem[MEM_STATE].release(h->d_heads);
         h->d_heads = nullptr; h->heads_L = 0;
     }
-    const size_t n = 2 * (size_t)h->R_ext * h->S.C * L;
-    const int rc = dev_alloc(h, MEM_STATE, &h->d_heads, n);
-    if (rc) { h->d_heads = nullptr; return rc; }
-    h->heads_L = L;
-    HIPCHK(h, hipMemsetAsync(h->d_heads, 0xFF, n * sizeof(int), h->stream));      // (-1: empty lists until the first refresh)
-    return VDS_OK;
+    const int rc = ensure_block(h, &h->d_heads, 2 * (size_t)h->R_ext * h->S.C * L, 0xFF);      // (-1: empty lists until the first refresh)
+    if (h->d_heads) h->heads_L = L;
+    return rc;
 }
 
 static int idle_heads_device_impl(vds_handle *h, int32_t L, void **dev_ptr) {
@@ -2318,7 +2348,7 @@ static int idle_heads_device_impl(vds_handle *h, int32_t L, void **dev_ptr) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int rc = ensure_idle_heads(h, L);
     if (rc) return rc;
-    launch_idle_heads(h->S, h->D, L, h->d_heads, h->stream);
+    Chain(h->stream).add(emit_idle_heads, h->S, h->D, L, h->d_heads, 0, 0);
     HIPCHK(h, hipGetLastError());
     if (dev_ptr) *dev_ptr = h->d_heads;
     return VDS_OK;
@@ -2342,31 +2372,13 @@ int vds_read_idle_heads(vds_handle *h, int32_t L, int32_t *veh, int32_t *node) {
 // The fields of `Vehicle` that the tick path changes (objects.py:75-89) for every replica at once: k_vehicle_lists / k_vehicle_pull
 // (vds_vehicle_planes.hip) into the int32 [6][R_ext][V] block, made on the first request (it lives with the state tables: re-made
 // when they are).  read_lists_impl + read_vehicles_impl below are the specification of what the planes hold.
-static int ensure_vehicles(vds_handle *h) {
-    if (h->d_veh) return VDS_OK;
-    const size_t n = std::max<size_t>(6 * (size_t)h->R_ext * h->S.V, 1);
-    const int rc = dev_alloc(h, MEM_STATE, &h->d_veh, n);
-    if (rc) { h->d_veh = nullptr; return rc; }
-    HIPCHK(h, hipMemsetAsync(h->d_veh, 0xFF, n * sizeof(int), h->stream));        // (-1: "in neither container" until a plane's first refresh)
-    return VDS_OK;
-}
-
 static int vehicles_device_impl(vds_handle *h, int32_t planes, void **dev_ptr) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_vehicles_device: call vds_reset first");
     if (planes < 1 || planes > 63) return fail(h, VDS_EINVAL, "vds_vehicles_device: planes = %d is outside 1 .. 63", planes);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int rc = ensure_vehicles(h);
     if (rc) return rc;
-    const size_t RV = (size_t)h->R_ext * h->S.V;
-    // every element of a requested plane is written, whatever the tables hold: -1 first (runs of neighbouring planes in one call), then the scatter
-    for (int k = 0; k < 6 && RV > 0;) {
-        if (!(planes >> k & 1)) { ++k; continue; }
-        int e = k;
-        while (e < 6 && (planes >> e & 1)) ++e;
-        HIPCHK(h, hipMemsetAsync(h->d_veh + k * RV, 0xFF, (size_t)(e - k) * RV * sizeof(int), h->stream));
-        k = e;
-    }
-    if (RV > 0) launch_vehicle_planes(h->S, h->D, h->last_stepped, planes, h->d_veh, h->stream);
+    if ((size_t)h->R_ext * h->S.V > 0) { Chain c(h->stream); refresh_vehicles(c, h, h->last_stepped, planes, 0, 0); }
     HIPCHK(h, hipGetLastError());
     if (dev_ptr) *dev_ptr = h->d_veh;
     return VDS_OK;
@@ -2393,21 +2405,12 @@ int vds_read_vehicles_all(vds_handle *h, int32_t planes, int32_t *out) {
 // What each vehicle earned in the slot stepped last (MatchFunction's matches, :924-975): k_vehicle_outcomes_fill + k_vehicle_outcomes
 // (vds_vehicle_outcomes.hip) into the int32 [R_ext][V][4] block, made on the first request (it lives with the state tables: re-made
 // when they are).  Derived from `out` on request, like d_outc: nothing of it is kept between calls or saved in a snapshot.
-static int ensure_vehicle_outcomes(vds_handle *h) {
-    if (h->d_vout) return VDS_OK;
-    const size_t n = std::max<size_t>(4 * (size_t)h->R_ext * h->S.V, 4);
-    const int rc = dev_alloc(h, MEM_STATE, &h->d_vout, n);
-    if (rc) { h->d_vout = nullptr; return rc; }
-    return VDS_OK;          // (not cleared here: nobody sees the block before k_vehicle_outcomes_fill has written all of it)
-}
-
 static int vehicle_outcomes_device_impl(vds_handle *h, void **dev_ptr) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_vehicle_outcomes_device: call vds_reset first");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int rc = ensure_vehicle_outcomes(h);
     if (rc) return rc;
-    // every element is written, whatever the memory held: the -1 fill of every replica's rows, then the scatter of the slot's orders
-    if ((size_t)h->R_ext * h->S.V > 0) launch_vehicle_outcomes(h->S, h->D, std::max(h->last_stepped, 0), h->last_stepped >= 0 ? 1 : 0, h->d_vout, h->stream);
+    if ((size_t)h->R_ext * h->S.V > 0) { Chain c(h->stream); refresh_vehicle_outcomes(c, h, std::max(h->last_stepped, 0), h->last_stepped >= 0 ? 1 : 0, 0, 0); }
     HIPCHK(h, hipGetLastError());
     if (dev_ptr) *dev_ptr = h->d_vout;
     return VDS_OK;
@@ -2446,10 +2449,7 @@ static int *roster_off(vds_handle *h) { return h->d_roster + 3 * (size_t)h->R_ex
 static int ensure_idle_roster(vds_handle *h) {
     if (h->d_roster) return VDS_OK;
     if (h->S.C > IDLE_ROSTER_C_MAX) return fail(h, VDS_ECAPACITY, "vds_idle_roster_device: %d clusters; k_idle_roster keeps a replica's offsets in LDS, at most %d", h->S.C, (int)IDLE_ROSTER_C_MAX);
-    const size_t n = 3 * (size_t)h->R_ext * h->S.V + (size_t)h->R_ext * (h->S.C + 1);
-    const int rc = dev_alloc(h, MEM_STATE, &h->d_roster, n);
-    if (rc) { h->d_roster = nullptr; return rc; }
-    return VDS_OK;          // (not cleared here: nobody sees the block before k_idle_roster has written all of it)
+    return ensure_block(h, &h->d_roster, 3 * (size_t)h->R_ext * h->S.V + (size_t)h->R_ext * (h->S.C + 1), -1);
 }
 
 static int idle_roster_device_impl(vds_handle *h, void **dev_planes, void **dev_off) {
@@ -2457,7 +2457,7 @@ static int idle_roster_device_impl(vds_handle *h, void **dev_planes, void **dev_
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int rc = ensure_idle_roster(h);
     if (rc) return rc;
-    launch_idle_roster(h->S, h->D, h->d_roster, roster_off(h), h->stream);
+    Chain(h->stream).add(emit_idle_roster, h->S, h->D, h->d_roster, roster_off(h), 0, 0);
     HIPCHK(h, hipGetLastError());
     h->roster_fresh = true;
     if (dev_planes) *dev_planes = h->d_roster;
@@ -2926,57 +2926,44 @@ static int read_vehicles_impl(vds_handle *h, int32_t replica, uint8_t *state, in
 }
 
 static int apply_dispatch_device_impl(vds_handle *h, int32_t K, const void *dev_actions) {
-    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_apply_dispatch_device: call vds_reset first");
-    if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_apply_dispatch_device: must follow vds_step of the current tick (the hook runs after Match, :1083)");
-    if (K == 0) return VDS_OK;
-    if (K < 0 || K > 64 || !dev_actions) return fail(h, VDS_EINVAL, "vds_apply_dispatch_device: K must be in [0, 64] and the action tensor non-null");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->roster_fresh = false;
-    if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
-    if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + K >= (1 << DENSE_ID_BITS))
-        return fail(h, VDS_ECAPACITY, "vds_apply_dispatch_device: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
-    launch_dispatch_dense(h->S, h->D, h->t, K, (const int *)dev_actions, h->dispatch_seq - h->seq_tick0, h->stream);
+    int seq_base;
+    const int rc = dispatch_begin(h, "vds_apply_dispatch_device", K, [&] {
+        return K < 0 || K > 64 || !dev_actions ? fail(h, VDS_EINVAL, "vds_apply_dispatch_device: K must be in [0, 64] and the action tensor non-null") : VDS_OK;
+    }, &seq_base);
+    if (rc || seq_base < 0) return rc;
+    launch_dispatch_dense(h->S, h->D, h->t, K, (const int *)dev_actions, seq_base, h->stream);
     HIPCHK(h, hipGetLastError());
-    h->dispatch_seq += K;
     return VDS_OK;
 }
 
 // The DispatchFunction body from one target node per vehicle (k_dispatch_vehicles, vds_dispatch_vehicles.hip): sequence number of a
 // vehicle's entry = the numbers the slot's earlier calls used + its vehicle number; the call uses up V of them.
+// (no vehicles: a [replicas][0] tensor has no address, and there is nothing to read from it - n == 0)
 static int apply_dispatch_vehicles_device_impl(vds_handle *h, const void *dev_targets) {
-    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: call vds_reset first");
-    if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: must follow vds_step of the current tick (the hook runs after Match, :1083)");
-    if (h->S.V <= 0) return VDS_OK;          // (no vehicles: a [replicas][0] tensor has no address, and there is nothing to read from it)
-    if (!dev_targets) return fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: the target tensor is null");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->roster_fresh = false;
-    if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
-    if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + h->S.V >= (1 << DENSE_ID_BITS))
-        return fail(h, VDS_ECAPACITY, "vds_apply_dispatch_vehicles_device: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
-    launch_dispatch_vehicles(h->S, h->D, h->t, (const int *)dev_targets, h->dispatch_seq - h->seq_tick0, h->stream);
+    int seq_base;
+    const int rc = dispatch_begin(h, "vds_apply_dispatch_vehicles_device", h ? std::max(h->S.V, 0) : 0, [&] {
+        return dev_targets ? VDS_OK : fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: the target tensor is null");
+    }, &seq_base);
+    if (rc || seq_base < 0) return rc;
+    Chain(h->stream).add(emit_dispatch_vehicles, h->S, h->D, h->t, (const int *)dev_targets, seq_base, 0, 0);
     HIPCHK(h, hipGetLastError());
-    h->dispatch_seq += h->S.V;
     return VDS_OK;
 }
 
-// The DispatchFunction body from one target node per ROSTER entry (k_dispatch_roster, vds_idle_roster.hip): sequence number of an
-// entry = the numbers the slot's earlier calls used + its roster position; the call uses up V of them.  The tensor only means
+// The DispatchFunction body from one target node per ROSTER entry (k_dispatch_roster, vds_dispatch_vehicles.hip): sequence number of
+// an entry = the numbers the slot's earlier calls used + its roster position; the call uses up V of them.  The tensor only means
 // something against the lists the block describes: refused unless the block was refreshed since the last call that can change one.
 static int apply_dispatch_roster_device_impl(vds_handle *h, const void *dev_targets) {
-    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_apply_dispatch_roster_device: call vds_reset first");
-    if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_apply_dispatch_roster_device: must follow vds_step of the current tick (the hook runs after Match, :1083)");
-    if (h->S.V <= 0) return VDS_OK;          // (no vehicles: a [replicas][0] tensor has no address, and there is nothing to read from it)
-    if (!dev_targets) return fail(h, VDS_EINVAL, "vds_apply_dispatch_roster_device: the target tensor is null");
-    if (!h->roster_fresh || !h->d_roster)
-        return fail(h, VDS_ESTATE, "vds_apply_dispatch_roster_device: the idle roster is stale - the idle lists may have changed since it was refreshed (a step, a dispatch call, a reset, a restore); call vds_idle_roster_device and write the targets against that roster");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (h->seq_tick != h->t) { h->seq_tick = h->t; h->seq_tick0 = h->dispatch_seq; }
-    if (h->S.dense && (long long)(h->dispatch_seq - h->seq_tick0) + h->S.V >= (1 << DENSE_ID_BITS))
-        return fail(h, VDS_ECAPACITY, "vds_apply_dispatch_roster_device: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
-    h->roster_fresh = false;
-    launch_dispatch_roster(h->S, h->D, h->t, (const int *)dev_targets, roster_off(h), h->dispatch_seq - h->seq_tick0, h->stream);
+    int seq_base;
+    const int rc = dispatch_begin(h, "vds_apply_dispatch_roster_device", h ? std::max(h->S.V, 0) : 0, [&] {
+        if (!dev_targets) return fail(h, VDS_EINVAL, "vds_apply_dispatch_roster_device: the target tensor is null");
+        if (!h->roster_fresh || !h->d_roster)
+            return fail(h, VDS_ESTATE, "vds_apply_dispatch_roster_device: the idle roster is stale - the idle lists may have changed since it was refreshed (a step, a dispatch call, a reset, a restore); call vds_idle_roster_device and write the targets against that roster");
+        return VDS_OK;
+    }, &seq_base);
+    if (rc || seq_base < 0) return rc;
+    Chain(h->stream).add(emit_dispatch_roster, h->S, h->D, h->t, (const int *)dev_targets, roster_off(h), seq_base, 0, 0);
     HIPCHK(h, hipGetLastError());
-    h->dispatch_seq += h->S.V;
     return VDS_OK;
 }
 

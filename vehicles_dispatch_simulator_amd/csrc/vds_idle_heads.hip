@@ -81,9 +81,4 @@ void emit_idle_heads(const Emit &e, const Static &S0, const State &D, int L, int
     emit_kernel(e, k_idle_heads, grid, block, 0, S, D, L, r_lo + n, heads);
 }
 
-void launch_idle_heads(const Static &S, const State &D, int L, int *heads, hipStream_t st) {
-    Emit e; e.st = st;
-    emit_idle_heads(e, S, D, L, heads, 0, 0);
-}
-
 }  // namespace vds

@@ -8,12 +8,12 @@
 //                                2 cluster  the cluster whose list holds it
 //   off    int32 [R_ext][C + 1]  off[r][c]: roster position of the head of Clusters[c].IdleVehicles; off[r][C]: idle vehicles of replica r
 // Entry i = off[r][c] + p is list position p of cluster c (the idle_pos of the other dispatch calls); all three planes hold -1 from
-// off[r][C] on.  k_idle_roster writes EVERY element of the block whatever the memory held; k_dispatch_roster is the DispatchFunction
-// body from a target tensor indexed by roster position (vds_apply_dispatch_roster_device; include/vds.h has both contracts).
+// off[r][C] on.  k_idle_roster writes EVERY element of the block whatever the memory held (vds_idle_roster_device; include/vds.h
+// has the contract).  The dispatch from a target tensor indexed by roster position is k_dispatch_roster, vds_dispatch_vehicles.hip.
 // Why a roster.  The per-vehicle planes and the vehicle-form dispatch are keyed by vehicle id, and inside a list the ids are in no
 // order: every 4-byte store or gather there is a 64-byte line of its own.  Keyed by roster position the refresh's stores, a policy's
 // reads and the dispatch's target loads are contiguous runs.
-// The lists are compact wherever the entry points run either kernel (vds_step and vds_run_hooked flush the stamp form every slot):
+// The lists are compact wherever the entry points run the kernel (vds_step and vds_run_hooked flush the stamp form every slot):
 // HDR_RAW == 0, checked in the WKDEBUG build.
 // This file is hashed with the HOST sources (Makefile): it is not one of the tick kernels the profiles/ evidence refers to.
 #include "vds_kernels_common.h"
@@ -157,105 +157,6 @@ void emit_idle_roster(const Emit &e, const Static &S0, const State &D, int *plan
     S.r_lo = r_lo;
     const int n = r_n > 0 ? r_n : S.R - r_lo;
     emit_kernel(e, k_idle_roster, dim3(n), dim3(IR_THREADS), idle_roster_lds(S), S, D, planes, off);
-}
-
-void launch_idle_roster(const Static &S, const State &D, int *planes, int *off, hipStream_t st) {
-    Emit e; e.st = st;
-    emit_idle_roster(e, S, D, planes, off, 0, 0);
-}
-
-// ---- k_dispatch_roster: k_dispatch_vehicles (vds_dispatch_vehicles.hip has the reasoning: the arrival entry's KEY carries dict
-// insertion order, so the buckets are independent) with the target of list position i of bucket (c, ext) read from
-// targets[ext][off[ext][c] + i] - the lanes of a chunk load one contiguous run - and the key id seq_base + off[ext][c] + i: the
-// order among the call's entries is ROSTER order, cluster then list position.  One wavefront per bucket, chunks of 64 entries,
-// ballot / lanemask_lt compaction in place, nothing stored while nothing has moved, lane 0 updates HDR_IDLE and the bucket's own
-// counters, DR_WAVES wavefronts on consecutive replicas of one cluster.  Plain vector loads and stores, no LDS.
-// Backstop: a bucket whose offsets do not describe its list as it stands (off[c + 1] - off[c] != HDR_IDLE, or a run outside [0, V])
-// applies nothing and raises ERR_DISPATCH - the tensor was written against other lists.  So no target beyond the row is ever read.
-// Refused as in the vehicle form (sticky ERR_DISPATCH, the vehicle stays, nothing of it is posted): a target >= N, a target node in
-// no cluster, a non-negative target in a replica whose order day is over.  Entries at or beyond off[ext][C] are never looked at.
-// Byte model: k_dispatch_vehicles' with the 4-byte gather counted as contiguous, + 8 B of offsets per bucket.
-#define DR_WAVES 4               // wavefronts (buckets: consecutive replicas of one cluster) per workgroup
-
-// targets: int32 [R_ext][V] by roster position; off: int32 [R_ext][C + 1] of the refresh the tensor was written against.
-// Grid: x = cluster, y = runs of DR_WAVES replicas from S.r_lo on (stored order), up to r_end.
-__global__ __launch_bounds__(DR_WAVES * WAVE) void k_dispatch_roster(Static S, State D, int t, int r_end, const int *__restrict__ targets, const int *__restrict__ off, int seq_base) {
-    const int c = (int)blockIdx.x;
-    const int r = S.r_lo + (int)blockIdx.y * DR_WAVES + (int)(threadIdx.x / WAVE);
-    if (r >= r_end) return;
-    const int ext = S.int2ext ? S.int2ext[r] : r;          // the tensor is indexed by the caller's replica (-1: padding replica)
-    if (ext < 0) return;
-    const int lane = lane_id();
-    const DayView dvw = day_view(S, r);
-    const bool over = t >= dvw.T;                           // the replica's day is over (:1048), its city stands still: targets are refused
-    const int now = dvw.now0 + t * S.tick_minutes;
-    const size_t b = (size_t)c * S.R + r;
-    int *hdr = D.hdr + b * HDR_WORDS;
-    const IdleRef idle = idle_ref(S, D, c, r);
-    const int len = hdr[HDR_IDLE];
-#ifdef WKDEBUG
-    if (lane == 0 && hdr[HDR_RAW] != 0) printf("k_dispatch_roster: raw list (HDR_RAW %d) c %d r %d\n", hdr[HDR_RAW], c, r);
-#endif
-    const int *offr = off + (size_t)ext * (S.C + 1);
-    const int o0 = offr[c], o1 = offr[c + 1];
-    if (o0 < 0 || o1 > S.V || o1 - o0 != len) {             // the roster is not this list's: nothing of the bucket is applied
-        if (lane == 0) atomicOr(&D.err[0], ERR_DISPATCH);
-        return;
-    }
-    const int m = max(min(len, S.idle_cap), 0);            // (never read beyond the table; m <= len, so o0 + i < o1 <= V below)
-    const int *tg = targets + (size_t)ext * S.V + o0;
-    const int coff = S.cl_off[c];
-    int newm = 0, nmove = 0;
-    long long cost_sum = 0;
-    bool bad = false;
-    for (int base = 0; base < m; base += WAVE) {
-        const int i = base + lane;
-        const bool in = i < m;
-        const uint2 e = in ? idle.get(i) : make_uint2(0u, 0u);
-        const int tgt = in ? tg[i] : -1;
-        const bool want = tgt >= 0;
-        bool move = want && !over && tgt < S.N;
-        int tc = -1;
-        if (move) { tc = S.node2cluster[tgt]; move = tc >= 0; }
-        bad = bad || (want && !move);
-        int cst = 0;
-        if (move) {
-            cst = S.cost[(size_t)tgt * S.N + coff + e.y];  // RoadCost(LocationNode, target)
-            post_arrival<false, true>(S, D, tc, r, t, now, (int)e.x, seq_base + o0 + i, now + cst, 1, S.node_local[tgt]);
-        }
-        const bool keep = in && !move;
-        const unsigned long long kb = ballot(keep);
-        wave_fence();
-        const int pos = newm + popc64(kb & lanemask_lt());
-        if (keep && pos != i) idle.set(pos, e);
-        newm += popc64(kb);
-        nmove += popc64(ballot(move));
-        // (64-bit sum: the wide layout takes any int32 cost, and 64 of them can pass 2^31)
-        long long cs = move ? (long long)cst : 0ll;
-        for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o, WAVE);
-        cost_sum += cs;
-        wave_fence();
-    }
-    if (ballot(bad) && lane == 0) atomicOr(&D.err[0], ERR_DISPATCH);
-    if (nmove > 0 && lane == 0) {
-        hdr[HDR_IDLE] = newm;
-        long long *cnt = D.cnt + b * CNT_WORDS;
-        cnt[CNT_DISPATCH] += nmove;
-        cnt[CNT_DISPATCH_COST] += cost_sum;
-    }
-}
-
-void emit_dispatch_roster(const Emit &e, const Static &S0, const State &D, int t, const int *targets, const int *off, int seq_base, int r_lo, int r_n) {
-    Static S = S0;
-    S.r_lo = r_lo;
-    const int n = r_n > 0 ? r_n : S.R - r_lo;
-    const dim3 grid(S.C, (n + DR_WAVES - 1) / DR_WAVES), block(DR_WAVES * WAVE);
-    emit_kernel(e, k_dispatch_roster, grid, block, 0, S, D, t, r_lo + n, targets, off, seq_base);
-}
-
-void launch_dispatch_roster(const Static &S, const State &D, int t, const int *targets, const int *off, int seq_base, hipStream_t st) {
-    Emit e; e.st = st;
-    emit_dispatch_roster(e, S, D, t, targets, off, seq_base, 0, 0);
 }
 
 }  // namespace vds

@@ -1,8 +1,9 @@
 // Host-side launchers of the kernel files, as vds_api.hip calls them: declarations only (included by vds_api.hip and by every file that
 // defines one of them; hashed with the HOST sources: Makefile).
-//   launch_*  on a stream
+//   launch_*  on a stream (the tick files only: the derived blocks and the tensor dispatch forms have no such twin)
 //   emit_*    on a stream or as a kernel node of an explicitly built hipGraph (Emit, vds_device.h), for the replicas
-//             [r_lo, r_lo + r_n) - r_lo a multiple of 16; r_n <= 0 (with r_lo 0): all
+//             [r_lo, r_lo + r_n) - r_lo a multiple of 16; r_n <= 0 (with r_lo 0): all.  One kernel each: which kernels refresh a
+//             block, in what order and when, is said once, by vds_api.hip (refresh_*)
 #pragma once
 #include "vds_device.h"
 
@@ -51,38 +52,31 @@ void launch_start_nodes_check(const int *veh_node, int R, int N, int V, int C, c
                               hipStream_t st);
 // ---- vds_outcomes.hip
 void emit_slot_outcomes(const Emit &e, const Static &S, const State &D, int t, int stepped, long long *oc, int r_lo, int r_n);
-void launch_slot_outcomes(const Static &S, const State &D, int t, int stepped, long long *oc, hipStream_t st);
 // ---- vds_idle_heads.hip
 void emit_idle_heads(const Emit &e, const Static &S, const State &D, int L, int *heads, int r_lo, int r_n);
-void launch_idle_heads(const Static &S, const State &D, int L, int *heads, hipStream_t st);
 // ---- vds_vehicle_planes.hip
 // t_last: slot stepped last (-1: none since the reset); planes: bit k = plane k of the int32 [6][R_ext][V] block `out` is wanted (the
-// caller has filled those with -1).  Two kernels, one launcher each (a graph node each): the bucket containers, and - when
+// fill has written -1 there).  Three kernels, one launcher each (a graph node each): the -1 fill, the bucket containers, and - when
 // vehicle_pull_needed - the static arrival slots
-void emit_vehicle_fill(const Emit &e, const Static &S, int planes, int *out, int r_lo, int r_n);      // the -1 fill as a kernel (day graph)
+void emit_vehicle_fill(const Emit &e, const Static &S, int planes, int *out, int r_lo, int r_n);
 void emit_vehicle_lists(const Emit &e, const Static &S, const State &D, int t_last, int planes, int *out, int r_lo, int r_n);
 bool vehicle_pull_needed(const Static &S, int t_last);
 void emit_vehicle_pull(const Emit &e, const Static &S, const State &D, int t_last, int planes, int *out, int r_lo, int r_n);
-void launch_vehicle_planes(const Static &S, const State &D, int t_last, int planes, int *out, hipStream_t st);
 // ---- vds_vehicle_outcomes.hip
 // blk: int32 [R_ext][V][4] {order, wait, value, pickup} per vehicle (16-byte aligned); t: slot stepped last, stepped == 0: none since
 // the reset.  Two kernels, one launcher each (a graph node each): the -1 fill of the replicas' rows, then the scatter of the slot's orders
 void emit_vehicle_outcomes_fill(const Emit &e, const Static &S, int *blk, int r_lo, int r_n);
 void emit_vehicle_outcomes(const Emit &e, const Static &S, const State &D, int t, int stepped, int *blk, int r_lo, int r_n);
-void launch_vehicle_outcomes(const Static &S, const State &D, int t, int stepped, int *blk, hipStream_t st);
-// ---- vds_dispatch_vehicles.hip
+// ---- vds_dispatch_vehicles.hip: one walk, two forms
 // targets: int32 [R_ext][V] target node per vehicle (negative: stay); seq_base: sequence numbers the slot's earlier dispatch calls used
 void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, int seq_base, int r_lo, int r_n);
-void launch_dispatch_vehicles(const Static &S, const State &D, int t, const int *targets, int seq_base, hipStream_t st);
+// targets: int32 [R_ext][V] target node per roster entry (negative: stay), against the offsets `off` of the refresh it was written for
+void emit_dispatch_roster(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *off, int seq_base, int r_lo, int r_n);
 // ---- vds_idle_roster.hip
 // planes: int32 [3][R_ext][V] {veh, node, cluster} by roster position, off: int32 [R_ext][C + 1]; one kernel writes every element of both
 // (dynamic LDS: idle_roster_lds, (C + 1) ints - C <= IDLE_ROSTER_C_MAX)
 enum { IDLE_ROSTER_C_MAX = 16000 };
 void emit_idle_roster(const Emit &e, const Static &S, const State &D, int *planes, int *off, int r_lo, int r_n);
-void launch_idle_roster(const Static &S, const State &D, int *planes, int *off, hipStream_t st);
-// targets: int32 [R_ext][V] target node per roster entry (negative: stay), against the offsets `off` of the refresh it was written for
-void emit_dispatch_roster(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *off, int seq_base, int r_lo, int r_n);
-void launch_dispatch_roster(const Static &S, const State &D, int t, const int *targets, const int *off, int seq_base, hipStream_t st);
 // ---- vds_snapshot.hip
 // the tables of a snapshot, one launch each: `src` -> `dst` are State views of the live tables and of the store (either way round),
 // map [S.R] stored replica -> stored source replica (null: identity), tdone the slots whose orders have been processed (SNAP_OUT)

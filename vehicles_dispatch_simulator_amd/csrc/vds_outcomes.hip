@@ -109,9 +109,4 @@ void emit_slot_outcomes(const Emit &e, const Static &S0, const State &D, int t, 
     emit_kernel(e, k_slot_outcomes, grid, block, 0, S, D, t, stepped, lpb, r_lo + n, oc);
 }
 
-void launch_slot_outcomes(const Static &S, const State &D, int t, int stepped, long long *oc, hipStream_t st) {
-    Emit e; e.st = st;
-    emit_slot_outcomes(e, S, D, t, stepped, oc, 0, 0);
-}
-
 }  // namespace vds

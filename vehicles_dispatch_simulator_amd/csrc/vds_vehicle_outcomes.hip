@@ -94,10 +94,4 @@ void emit_vehicle_outcomes(const Emit &e, const Static &S0, const State &D, int 
     emit_kernel(e, k_vehicle_outcomes, grid, block, 0, S, D, t, stepped, r_lo + n, (int4 *)blk);
 }
 
-void launch_vehicle_outcomes(const Static &S, const State &D, int t, int stepped, int *blk, hipStream_t st) {
-    Emit e; e.st = st;
-    emit_vehicle_outcomes_fill(e, S, blk, 0, 0);
-    if (stepped && S.Oq > 0) emit_vehicle_outcomes(e, S, D, t, stepped, blk, 0, 0);
-}
-
 }  // namespace vds

@@ -240,8 +240,8 @@ __global__ __launch_bounds__(VP_THREADS) void k_vehicle_pull(Static S, State D, 
         if (fly[u]) veh_store(o, ext[u], (int)(en[u] >> 8), 1, node[u], rec[u].z & 0xFFFF, now0[u] + ry[u] * S.tick_minutes + rs[u].y + rec[u].w, rec[u].x, SRC_PULL);
 }
 
-// The -1 fill of the requested planes as a kernel (the per-slot refresh inside vds_run_hooked's day graph, which carries kernel nodes
-// only; the entry points on a stream fill with hipMemsetAsync): the rows of the replicas [S.r_lo, r_end) (stored order).
+// The -1 fill of the requested planes, ahead of the scatter: the rows of the replicas [S.r_lo, r_end) (stored order).  A kernel, so
+// that the refresh is one sequence on a stream and inside vds_run_hooked's day graph, which carries kernel nodes only.
 // Grid: x = replica, y = runs of VP_THREADS vehicles.
 __global__ __launch_bounds__(VP_THREADS) void k_vehicle_fill(Static S, int planes, int r_end, int *__restrict__ out) {
     const int v = (int)blockIdx.y * VP_THREADS + (int)threadIdx.x;
@@ -282,12 +282,6 @@ void emit_vehicle_pull(const Emit &e, const Static &S0, const State &D, int t_la
     const long long win = std::min<long long>((long long)(S.pull_hmax + S.pull_W) * std::max(S.max_tick_orders, 1), S.Oq);
     const dim3 grid((unsigned)((std::max<long long>(win, 1) + VP_THREADS - 1) / VP_THREADS), (n + VP_RPT - 1) / VP_RPT), block(VP_THREADS);
     emit_kernel(e, k_vehicle_pull, grid, block, 0, S, D, t_last, planes, r_lo + n, out);
-}
-
-void launch_vehicle_planes(const Static &S, const State &D, int t_last, int planes, int *out, hipStream_t st) {
-    Emit e; e.st = st;
-    emit_vehicle_lists(e, S, D, t_last, planes, out, 0, 0);
-    if (vehicle_pull_needed(S, t_last)) emit_vehicle_pull(e, S, D, t_last, planes, out, 0, 0);
 }
 
 }  // namespace vds

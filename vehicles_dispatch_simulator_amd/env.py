@@ -28,6 +28,19 @@ def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _device_tensor(ptr: int, shape, typestr: str, device: int, strides=None):
+    """Zero-copy ``torch`` tensor over library memory at device pointer ``ptr`` (the CUDA array interface; ``strides`` in bytes,
+    ``None``: contiguous)."""
+    import torch
+
+    class _Block:
+        pass
+
+    blk = _Block()
+    blk.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (ptr, False), "version": 2, "strides": strides}
+    return torch.as_tensor(blk, device=torch.device("cuda", device))
+
+
 def neighbors_to_csr(neighbors: Sequence[Sequence[int]]):
     off = np.zeros(len(neighbors) + 1, dtype=np.int32)
     off[1:] = np.cumsum([len(x) for x in neighbors])
@@ -425,34 +438,18 @@ class BatchedDispatchEnv:
         host round trip.  The tensor aliases library memory and is overwritten by the next call.
         ``inflight=False`` leaves the fifth plane (``len(Cluster.VehiclesArrivetime)``) as it was: the pass then reads
         a third of the arrival tables (per-slot hooks that do not use it)."""
-        import torch
-
-        class _Block:
-            pass
-
-        blk = _Block()
-        blk.__cuda_array_interface__ = {"shape": (5, self.R, self.C), "typestr": "<i4", "data": (self.obs_device_ptr((1 if idle_pre else 0) | (2 if idle_now else 0) | (4 if supply else 0) | (8 if cl_orders else 0) | (16 if inflight else 0)), False),
-                                        "version": 2, "strides": None}
-        return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+        ptr = self.obs_device_ptr((1 if idle_pre else 0) | (2 if idle_now else 0) | (4 if supply else 0) | (8 if cl_orders else 0) | (16 if inflight else 0))
+        return _device_tensor(ptr, (5, self.R, self.C), "<i4", self.device)
 
     def obs_inplace_torch(self):
         """``idle_pre``, ``idle_now`` and ``cl_orders`` as zero-copy strided ``torch`` int32 views ``[R, C]`` of the bucket records
         the tick kernels keep (``vds_obs_inplace``): always current, no pass per slot - what a device-side policy that does not
         need ``supply`` / ``inflight`` reads.  Read-only.  Raises when the replicas are stored regrouped by order day."""
-        import torch
-
         out = {}
         for name, k in (("idle_pre", 0), ("idle_now", 1), ("cl_orders", 3)):
             p, sr, sc = C.c_void_p(), C.c_int64(), C.c_int64()
             self._chk(self._lib.vds_obs_inplace(self._h, k, C.byref(p), C.byref(sr), C.byref(sc)))
-
-            class _Block:
-                pass
-
-            blk = _Block()
-            blk.__cuda_array_interface__ = {"shape": (self.R, self.C), "typestr": "<i4", "data": (p.value, False), "version": 2,
-                                            "strides": (4 * sr.value, 4 * sc.value)}
-            out[name] = torch.as_tensor(blk, device=torch.device("cuda", self.device))
+            out[name] = _device_tensor(p.value, (self.R, self.C), "<i4", self.device, strides=(4 * sr.value, 4 * sc.value))
         return out
 
     def supply_inplace_torch(self):
@@ -460,38 +457,19 @@ class BatchedDispatchEnv:
         order day): ``(ring, slot)`` - ``ring`` a zero-copy int32 view ``[32, R, C]`` of the per-arrival-slot counters, ``slot`` a
         device int32 tensor ``[1]`` holding the plane of the slot stepped last.  ``ring[slot]`` (``ring.index_select(0, slot)[0]``) is
         ``SupplyExpect`` of that slot; both tensors keep their addresses, so a policy captured as a graph may read them every slot."""
-        import torch
-
         ring, slot, planes = C.c_void_p(), C.c_void_p(), C.c_int32()
         sp, sr, sc = C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self._lib.vds_supply_inplace(self._h, C.byref(ring), C.byref(sp), C.byref(sr), C.byref(sc), C.byref(slot), C.byref(planes)))
-
-        class _Block:
-            pass
-
-        blk = _Block()
-        blk.__cuda_array_interface__ = {"shape": (planes.value, self.R, self.C), "typestr": "<i4", "data": (ring.value, False), "version": 2,
-                                        "strides": (4 * sp.value, 4 * sr.value, 4 * sc.value)}
-        sw = _Block()
-        sw.__cuda_array_interface__ = {"shape": (1,), "typestr": "<i4", "data": (slot.value, False), "version": 2}
-        dev = torch.device("cuda", self.device)
-        return torch.as_tensor(blk, device=dev), torch.as_tensor(sw, device=dev)
+        return (_device_tensor(ring.value, (planes.value, self.R, self.C), "<i4", self.device, strides=(4 * sp.value, 4 * sr.value, 4 * sc.value)),
+                _device_tensor(slot.value, (1,), "<i4", self.device))
 
     def counters_torch(self):
         """Per-replica counters as a zero-copy ``torch`` int64 tensor ``[R, 8]`` on the GPU, in device order
         ``(orders, rejects, wait_sum, matched_value_sum, evals, arrivals, dispatch_num, dispatch_cost)``;
         aliases library memory, overwritten by the next counter call."""
-        import torch
-
         p = C.c_void_p()
         self._chk(self._lib.vds_counters_device(self._h, C.byref(p)))
-
-        class _Block:
-            pass
-
-        blk = _Block()
-        blk.__cuda_array_interface__ = {"shape": (self.R, 8), "typestr": "<i8", "data": (p.value, False), "version": 2, "strides": None}
-        return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+        return _device_tensor(p.value, (self.R, 8), "<i8", self.device)
 
     def outcomes_device_ptr(self) -> int:
         """Device pointer of the int64 ``[4][R][C]`` outcome block, computed for the slot stepped last (``vds_outcomes_device``)."""
@@ -504,15 +482,7 @@ class BatchedDispatchEnv:
         ``served`` (``ArriveInfo == "Success"``), ``rejected`` (``"Reject"``), ``wait_sum`` (``PickupWaitTime`` of the served) and
         ``value_sum`` (``OrderValue`` of the served) over the orders that ``Cluster.Orders`` holds during the slot's hooks
         (``simulator.py:919-1013``).  Aliases library memory, overwritten by the next outcome call or by ``run_hooked(outcomes=True)``."""
-        import torch
-
-        class _Block:
-            pass
-
-        blk = _Block()
-        blk.__cuda_array_interface__ = {"shape": (4, self.R, self.C), "typestr": "<i8", "data": (self.outcomes_device_ptr(), False),
-                                        "version": 2, "strides": None}
-        return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+        return _device_tensor(self.outcomes_device_ptr(), (4, self.R, self.C), "<i8", self.device)
 
     def outcomes(self) -> Dict[str, np.ndarray]:
         """``outcomes_torch`` copied to the host: ``{served, rejected, wait_sum, value_sum}``, each int64 ``[R, C]``."""
@@ -532,15 +502,7 @@ class BatchedDispatchEnv:
         ``[2, R, C, L]`` on the GPU: plane 0 ``Vehicle.ID``, plane 1 ``Vehicle.LocationNode`` (global node id), ``-1`` past the end of a
         list.  The last index is the ``idle_pos`` of ``apply_dispatch*`` (``simulator.py:893-898``).  Refreshed by this call; aliases
         library memory, overwritten by the next heads call or by ``run_hooked(idle_heads=L)``."""
-        import torch
-
-        class _Block:
-            pass
-
-        blk = _Block()
-        blk.__cuda_array_interface__ = {"shape": (2, self.R, self.C, int(L)), "typestr": "<i4", "data": (self.idle_heads_device_ptr(L), False),
-                                        "version": 2, "strides": None}
-        return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+        return _device_tensor(self.idle_heads_device_ptr(L), (2, self.R, self.C, int(L)), "<i4", self.device)
 
     def idle_heads(self, L: int) -> Dict[str, np.ndarray]:
         """``idle_heads_torch`` copied to the host: ``{veh, node}``, each int32 ``[R, C, L]``."""
@@ -623,15 +585,9 @@ class BatchedDispatchEnv:
 
         ks = self._vehicle_planes(state, node, cluster, arrive_min, order, source)
         ptr = self.vehicles_device_ptr(sum(1 << k for k in ks))
-
-        class _Block:
-            pass
-
-        blk = _Block()
-        blk.__cuda_array_interface__ = {"shape": (6, self.R, self.V), "typestr": "<i4", "data": (ptr, False), "version": 2, "strides": None}
         if self.R * self.V == 0:
             return {VEHICLE_PLANE_NAMES[k]: torch.empty((self.R, self.V), dtype=torch.int32, device=torch.device("cuda", self.device)) for k in ks}
-        t = torch.as_tensor(blk, device=torch.device("cuda", self.device))
+        t = _device_tensor(ptr, (6, self.R, self.V), "<i4", self.device)
         return {VEHICLE_PLANE_NAMES[k]: t[k] for k in ks}
 
     def vehicles_all(self, state=True, node=True, cluster=True, arrive_min=True, order=True, source=False) -> Dict[str, np.ndarray]:
@@ -660,13 +616,7 @@ class BatchedDispatchEnv:
         ptr = self.vehicle_outcomes_device_ptr()
         if self.R * self.V == 0:
             return torch.empty((self.R, self.V, 4), dtype=torch.int32, device=torch.device("cuda", self.device))
-
-        class _Block:
-            pass
-
-        blk = _Block()
-        blk.__cuda_array_interface__ = {"shape": (self.R, self.V, 4), "typestr": "<i4", "data": (ptr, False), "version": 2, "strides": None}
-        return torch.as_tensor(blk, device=torch.device("cuda", self.device))
+        return _device_tensor(ptr, (self.R, self.V, 4), "<i4", self.device)
 
     def vehicle_outcomes(self) -> Dict[str, np.ndarray]:
         """``vehicle_outcomes_torch`` copied to the host and de-interleaved (``vds_read_vehicle_outcomes``, synchronous):
@@ -694,20 +644,11 @@ class BatchedDispatchEnv:
         import torch
 
         pp, po = self.idle_roster_device_ptr()
-        dev = torch.device("cuda", self.device)
-
-        class _Block:
-            pass
-
-        bo = _Block()
-        bo.__cuda_array_interface__ = {"shape": (self.R, self.C + 1), "typestr": "<i4", "data": (po, False), "version": 2, "strides": None}
-        out = {"off": torch.as_tensor(bo, device=dev)}
+        out = {"off": _device_tensor(po, (self.R, self.C + 1), "<i4", self.device)}
         if self.R * self.V == 0:
-            out.update({k: torch.empty((self.R, self.V), dtype=torch.int32, device=dev) for k in IDLE_ROSTER_NAMES})
+            out.update({k: torch.empty((self.R, self.V), dtype=torch.int32, device=torch.device("cuda", self.device)) for k in IDLE_ROSTER_NAMES})
             return out
-        bp = _Block()
-        bp.__cuda_array_interface__ = {"shape": (3, self.R, self.V), "typestr": "<i4", "data": (pp, False), "version": 2, "strides": None}
-        t = torch.as_tensor(bp, device=dev)
+        t = _device_tensor(pp, (3, self.R, self.V), "<i4", self.device)
         out.update({k: t[i] for i, k in enumerate(IDLE_ROSTER_NAMES)})
         return out
 
