@@ -53,12 +53,22 @@ enum {
 
 typedef struct vds_handle vds_handle;
 
+/* Minutes are int32 throughout: RealExpTime of slot 0 is `first release - tick_minutes`, that of slot t is `now0 + t * tick_minutes`
+ * (t <= T), a slot's window ends at `now + tick_minutes - 1`.  The shortest day - a single order - has 5 slots (one before the first
+ * release, three behind the last, :1037-1040), so `5 * tick_minutes` must fit: vds_create refuses a longer slot.  Whether a given
+ * day fits depends on its release minutes: vds_load_orders* refuses (VDS_EINVAL) a day with `first release - tick_minutes` below
+ * INT32_MIN, or with `T * tick_minutes` or `now0 + T * tick_minutes` above INT32_MAX, T being its number of slots (at most 65535).
+ * What these checks do not cover is a trip's own length: the slots until an arrival are `(rel + tick_minutes - 1) / tick_minutes` with
+ * `rel` = wait + order value (or a dispatch cost), and the arrival minute is `now + rel`; both hold only while `rel` stays below
+ * `INT32_MAX - tick_minutes` and `now + rel` below INT32_MAX - costs are the caller's, and no load checks their sums. */
+#define VDS_TICK_MINUTES_MAX (INT32_MAX / 5)
+
 typedef struct vds_config {
     int32_t struct_size;              /* sizeof(vds_config), for forward compatibility */
     int32_t device;                   /* HIP device ordinal */
     int32_t replicas;                 /* R: independent cities held by this handle */
     int32_t vehicles;                 /* V per replica   (config/setting.py:23 VehiclesNumber) */
-    int32_t tick_minutes;             /* TIMESTEP in minutes (config/setting.py:6 -> 10) */
+    int32_t tick_minutes;             /* TIMESTEP in minutes (config/setting.py:6 -> 10): 1 .. VDS_TICK_MINUTES_MAX */
     int32_t neighbor_can_server;      /* config/setting.py:11 NeighborCanServer */
     int64_t pickup_reject_threshold;  /* raw integer of PICKUPTIMEWINDOW (config/setting.py:7 ->
                                          600000000000): `cost > PICKUPTIMEWINDOW` (:943) compares

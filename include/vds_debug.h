@@ -67,8 +67,10 @@ int vds_debug_cluster_forms(vds_handle *h, uint8_t *out, int64_t cap, int32_t *n
 /* the layout decision as the handle stands (tests/test_gpu_thresholds.py), cap >= 10 words: out[0] dense layout (k_tick_dense),
  * [1] its stamp form (neighbour search on the dense layout), [2] cost blocks of the dense layout: 1 bytes, 0 ints, [3] u8_ok (every cost
  * of the matrix in 0..255), [4] the byte copy of the whole matrix exists, [5] fast_ok (packed keys), [6] window_live, [7] seq_pad, [8]
- * lanes per replica of k_tick_dense, [9] its fast-path table size (128 / 256); -1 where a value does not apply (no orders loaded, no
- * dense layout, no neighbour search); words past 10 are -1. */
+ * lanes per replica of k_tick_dense, [9] its fast-path table size (128 / 256), and with cap >= 11 [10] the dense tick's arrival form:
+ * 1 static arrival slots, 0 the arrival ring (its own choice when arrivals can lie more than DENSE_PULL_WMAX slots behind their
+ * earliest slot, or the debug switch); -1 where a value does not apply (no orders loaded, no dense layout, no neighbour search);
+ * words past 11 are -1. */
 int vds_debug_layout(vds_handle *h, int32_t *out, int32_t cap);
 
 /* Host tables of a load without a handle or a device (csrc/vds_tables.h; tests/test_order_tables.py): the city of vds_load_static

@@ -131,13 +131,15 @@ def narrow(a):
 def generate(name, s):
     city = build_city(s)
     start, pick, dele = synth.make_orders(s["order_seed"], city.N, s["O"])
+    if s.get("span"):       # the day's release times stretched over span[0] / span[1] days (make_slot_golden.py: days of > 32767 slots)
+        start = start[0] + (start - start[0]) * s["span"][0] // s["span"][1]
     service_m = s["side_m"] * (s["depth"] + 0.5) + s["side_m"] / 32
     run = dict(V=s["V"], seed=s["veh_seed"], cluster_mode=s["cluster_mode"], side_m=s["side_m"], service_m=service_m,
                neighbor_can_server=s["neighbor"], tick_minutes=s["tick"], pickup_window_raw=s["window"])
     if s["extra"]:
         run["dispatch_extra_minutes"] = s["extra"]
-    out = rh.run_reference(city, start, pick, dele, dispatch_policy=policy_factory(city.N) if s["dispatch"] else None,
-                           capture_lists=True, focus_bound=s["focus"], **run)
+    out = rh.run_reference(city, start, pick, dele, dispatch_policy=policy_factory(city.N, every=s.get("every", 3)) if s["dispatch"] else None,
+                           capture_lists=s.get("lists", True), focus_bound=s["focus"], **run)
     # the generator's tables must be exactly what the reference loaded / derived
     assert int(out["C"]) == s["C"] and int(out["depth_limit"]) == s["depth"], (name, out["C"], out["depth_limit"])
     assert (out["cost"] == city.cost).all()
@@ -164,15 +166,17 @@ def generate(name, s):
                city_seed=np.int64(s["city_seed"]), order_seed=np.int64(s["order_seed"]), n_orders_raw=np.int64(s["O"]),
                style=np.str_(s["style"]), style_k=np.int64(s["style_k"]), empty=np.array(s["empty"], dtype=np.int32),
                focus_bound=np.array(s["focus"] or (), dtype=np.float64))
+    if s.get("span"):
+        out["span"] = np.array(s["span"], dtype=np.int64)
     return {k: narrow(v) for k, v in out.items()}
 
 
-def summary_line(name, g, size):
+def summary_line(name, g, size, width=11):
     f = helpers.recorded_day_facts(g)
     win = int(g["reject_threshold"])
-    return ("%-11s C=%-2d N=%-3d %-5s depth=%-2d nbr=%d tick=%-2d window=%-4s V=%-3d O=%-4d disp=%-3d ticks=%-3d rejects=%-4d "
+    return ("%-*s C=%-2d N=%-3d %-5s depth=%-2d nbr=%d tick=%-2d window=%-4s V=%-3d O=%-4d disp=%-3d ticks=%-3d rejects=%-4d "
             "by_window=%-4d own_empty=%-4d cross=%-3d empty_cl=%d %3.0fKB" % (
-                name, g["C"], g["N"], g["style"], g["depth_limit"], g["neighbor_can_server"], g["tick_minutes"],
+                width, name, g["C"], g["N"], g["style"], g["depth_limit"], g["neighbor_can_server"], g["tick_minutes"],
                 win if helpers.live_window(g) else "none", g["V"], g["order_num"], g["dispatch_num"], g["n_ticks"], g["reject_num"],
                 f["window_rejects"], f["empty_rejects"], f["cross"], helpers.clusters_without_nodes(g), size / 1024))
 

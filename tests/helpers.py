@@ -54,6 +54,42 @@ def load_fuzz(name):
     return g
 
 
+_SLOT_INDEX = None
+
+
+def _slot_index():
+    """case name -> pack file of the slot-length corpus (tests/golden/make_slot_golden.py, the fuzz corpus' file form)."""
+    global _SLOT_INDEX
+    if _SLOT_INDEX is None:
+        _SLOT_INDEX = {}
+        for p in sorted(glob.glob(os.path.join(GOLDEN_DIR, "slotpack_*.npz"))):
+            with np.load(p) as z:
+                for k in z.files:
+                    _SLOT_INDEX[k.split("/")[0]] = p
+    return _SLOT_INDEX
+
+
+def slot_names(long_days=None):
+    """The slot-length corpus; ``long_days``: only (True) / without (False) the days of more than 32767 slots."""
+    return sorted(n for n in _slot_index() if long_days is None or n.startswith("slot_long") == long_days)
+
+
+def forget_slot_index():
+    global _SLOT_INDEX
+    _SLOT_INDEX = None
+
+
+def load_slot(name):
+    """One case of the slot-length corpus in the form of a tiny fixture."""
+    g = {}
+    with np.load(_slot_index()[name]) as z:
+        for k in z.files:
+            if k.startswith(name + "/"):
+                a = z[k]
+                g[k[len(name) + 1:]] = a.astype(np.int32) if a.dtype == np.int16 else a
+    return g
+
+
 def live_window(g):
     """The fixture's raw pickup window can reject a vehicle that was found (below the reference's default, which no cost reaches)."""
     return engine_settings(g)["reject_threshold"] < DEFAULT_REJECT_THRESHOLD
@@ -66,6 +102,8 @@ def load_golden(name):
     (the generator asserted equality with what the reference loaded)."""
     if name.startswith("fuzz_"):
         return load_fuzz(name)
+    if name.startswith("slot_"):
+        return load_slot(name)
     g = dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz")))
     if "cost" not in g and str(g["city_mode"]) == "shipped":
         # the reference's shipped road graph and clustering (labels / neighbour lists are in the fixture);
@@ -190,6 +228,66 @@ def fuzz_coverage_gaps(cases):
     need("dispatch with a live window", lambda r: r["dispatch"] and r["window"] is not None)
     need("dispatch with depth >= 2", lambda r: r["dispatch"] and r["nbr"] and r["depth"] >= 2)
     need("nodes outside every cluster with depth >= 1 and a live window", lambda r: r["outside"] and r["nbr"] and r["depth"] >= 1 and r["window"] is not None)
+    return gaps
+
+
+SLOT_LENGTHS = (1, 2, 30, 60, 63, 64, 120, 1440)
+SIGN_SLOT = 32768           # from this slot on the 16-bit slot number of a packed meta word has its top bit set
+
+
+def dense_by_own_rules(g):
+    """The library runs the dense tick on this day by itself: no search beyond the pickup's cluster, no live window, byte costs."""
+    searching = bool(g["neighbor_can_server"]) and int(g["depth_limit"]) > 0
+    return not searching and not live_window(g) and int(g["cost"].min()) >= 0 and int(g["cost"].max()) <= 254
+
+
+def slot_day_facts(g):
+    """recorded_day_facts plus what the slot-length corpus is about, from the record alone: the slot each order was processed in
+    (``t_order_num`` is cumulative), the slots a served order's vehicle is under way (its wait and its value, rounded up), the
+    largest number of orders one slot processed."""
+    f = recorded_day_facts(g)
+    tick, T = int(g["tick_minutes"]), int(g["n_ticks"])
+    served = np.flatnonzero(g["o_status"] == 1)
+    slot = np.searchsorted(np.asarray(g["t_order_num"], np.int64), served, side="right")
+    trip = (g["o_wait"][served].astype(np.int64) + np.asarray(g["o_value"], np.int64)[served])
+    ahead = np.where(trip <= 0, 1, -(-trip // tick))
+    f.update(tick=tick, T=T, served=int(served.size), rejects=int(g["reject_num"]), dispatch=int(g["dispatch_num"]),
+             searching=bool(g["neighbor_can_server"]) and int(g["depth_limit"]) > 0, dense=dense_by_own_rules(g),
+             window=live_window(g), far=int((ahead >= 32).sum()), near=int((ahead < 32).sum()),
+             most=int(np.diff(np.concatenate([[0], np.asarray(g["t_order_num"], np.int64)])).max()),
+             served_late=int((slot >= SIGN_SLOT).sum()), across=int(((slot < SIGN_SLOT) & (slot + ahead > SIGN_SLOT)).sum()),
+             lists="l_idle_off" in g)
+    return f
+
+
+def slot_coverage_gaps(cases):
+    """The coverage conditions of the slot-length corpus (tests/golden/make_slot_golden.py) that ``cases`` leave unmet; asserted
+    empty by the generator and by tests/test_oracle_fuzz_golden.py."""
+    rows = [dict(slot_day_facts(g), name=n) for n, g in cases.items()]
+    gaps = []
+
+    def need(what, pred, n=1):
+        if sum(1 for r in rows if pred(r)) < n:
+            gaps.append(what)
+
+    for k in SLOT_LENGTHS:
+        short = lambda r, k=k: r["tick"] == k and r["T"] < SIGN_SLOT and r["lists"]
+        need("%d minutes three times" % k, short, 3)
+        need("%d minutes: a day for the dense tick" % k, lambda r: short(r) and r["dense"] and r["served"] > 0)
+        need("%d minutes: a searching day that served from another cluster" % k, lambda r: short(r) and r["searching"] and r["cross"] > 0)
+        need("%d minutes: a day with dispatch" % k, lambda r: short(r) and r["dispatch"] > 0)
+        need("%d minutes: served and rejected orders in one day" % k, lambda r: short(r) and r["served"] > 0 and r["rejects"] > 0)
+        if k <= 2:
+            need("%d minutes: trips of 32 slots and more beside shorter ones" % k, lambda r: short(r) and r["far"] > 0 and r["near"] > 0)
+        if k >= 60:
+            need("%d minutes: more than 256 orders in one slot" % k, lambda r: short(r) and r["most"] > 256)
+            need("%d minutes: rejects caused by a live window" % k, lambda r: short(r) and r["window"] and r["window_rejects"] > 0)
+    long_days = [r for r in rows if r["T"] > SIGN_SLOT - 1]
+    if len(long_days) != 2 or sorted(r["searching"] for r in long_days) != [False, True]:
+        gaps.append("two days of more than 32767 slots, one of them searching")
+    for r in long_days:
+        if not (r["served_late"] > 0 and r["across"] > 0 and r["dispatch"] == 0 and not r["lists"]):
+            gaps.append("%s: orders served from slot 32768 on and vehicles under way across it" % r["name"])
     return gaps
 
 

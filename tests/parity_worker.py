@@ -18,6 +18,8 @@ try:
         g = load_golden(name)
         if kind == "ragged":         # R not a multiple of the workgroup's replica run; every replica its own vehicle seed
             P.run_day(g, R=37, same_init=False, list_every=29, **P.MODES[mode])
+        elif kind.startswith("thin"):  # "thin<n>": a day of many slots - obs and counters at every slot, containers at every n-th and around dispatch
+            P.run_day(g, R=3, same_init=bool(len(g["dispatch_log"])), list_every=int(kind[4:]), **P.MODES[mode])
         else:
             P.run_day(g, R=3, same_init=bool(len(g["dispatch_log"])), **P.MODES[mode])
         done += 1

@@ -8,7 +8,9 @@ Row 10 covers the dispatch kernels: K = 64 / 65 device actions, more than 64 hos
 dispatch costs whose sum passes 2^31 (host lists, a device tensor, a hooked slot).
 
 Out of scope, the inputs being too large for a test: V >= 2^24 vehicles and >= 2^25 orders per day (the dense layout's packed ids),
-vds_reset_random's LDS limit of 15 760 clusters, and arrival minutes beyond int32."""
+vds_reset_random's LDS limit of 15 760 clusters, and arrival minutes beyond int32 (a slot length or a day whose own minutes do not
+fit is refused on the host: tests/test_order_tables.py, tests/test_slot_length_limits.py).  Every city here runs 10-minute slots; the
+slot-length axis, 1 .. 1440 minutes, and days beyond slot 32767 are tests/test_gpu_slot_lengths.py."""
 import os
 
 import numpy as np

@@ -8,18 +8,20 @@ import os
 import numpy as np
 import pytest
 
-from helpers import fuzz_coverage_gaps, fuzz_names, load_fuzz
+from helpers import SLOT_LENGTHS, fuzz_coverage_gaps, fuzz_names, load_fuzz, load_golden, slot_coverage_gaps, slot_names
 from oracle.ref_harness import write_reference_data_dir
 from test_oracle_golden import replay
 from vehicles_dispatch_simulator_amd import synth, world
 
 FUZZ = fuzz_names()
+SLOT = slot_names()
+LONG = slot_names(long_days=True)
 
 
-@pytest.mark.parametrize("name", FUZZ)
+@pytest.mark.parametrize("name", FUZZ + SLOT)
 def test_oracle_matches_reference_fuzz(name):
-    g = load_fuzz(name)
-    o = replay(g, check_lists=True)
+    g = load_golden(name)
+    o = replay(g, check_lists=name not in LONG)       # (only the two days of more than 32767 slots are recorded without lists)
     od = o.orders()
     np.testing.assert_array_equal(od["status"], g["o_status"])
     np.testing.assert_array_equal(od["vehicle"], g["o_vehicle"])
@@ -45,6 +47,21 @@ def test_fuzz_corpus_covers_its_axes():
     golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     sizes = [os.path.getsize(os.path.join(golden, f)) for f in os.listdir(golden) if f.startswith("fuzzpack_")]
     assert max(sizes) < 1_000_000 and sum(sizes) < 4_000_000
+
+
+def test_slot_corpus_covers_its_axes():
+    """The slot-length corpus (tests/golden/make_slot_golden.py): per slot length a day for the dense tick, a search that served from
+    another cluster, dispatch, served beside rejected orders; trips beyond the ring horizon at 1 and 2 minutes; slots of more than
+    256 orders and window rejects from 60 minutes on; two days that serve orders past slot 32767 with vehicles under way across it
+    (conditions: helpers.slot_coverage_gaps, from the reference's record alone)."""
+    cases = {n: load_golden(n) for n in SLOT}
+    assert slot_coverage_gaps(cases) == []
+    assert {int(g["tick_minutes"]) for g in cases.values()} == set(SLOT_LENGTHS)
+    assert sorted(slot_names(long_days=True)) == ["slot_long_pull", "slot_long_search"]
+    assert all(int(cases[n]["n_ticks"]) > 32767 for n in slot_names(long_days=True))
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    sizes = [os.path.getsize(os.path.join(golden, f)) for f in os.listdir(golden) if f.startswith("slotpack_")]
+    assert max(sizes) < 1_000_000 and sum(sizes) < 3_000_000
 
 
 def _loader_cases():

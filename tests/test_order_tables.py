@@ -9,11 +9,11 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import fuzz_names, golden_names, load_golden
+from helpers import fuzz_names, golden_names, load_golden, slot_names
 from vehicles_dispatch_simulator_amd import _lib, synth
 
 EINVAL, ECAPACITY, ESTATE = -1, -3, -4
-ALL_DAYS = golden_names("tiny_") + golden_names("real_") + fuzz_names()
+ALL_DAYS = golden_names("tiny_") + golden_names("real_") + fuzz_names() + slot_names()
 WMAX = 3          # DENSE_PULL_WMAX (csrc/vds_device.h)
 
 
@@ -135,6 +135,29 @@ def test_recorded_day(name):
     assert o["d_rec"].shape[0] == m and (o["W"], o["hmax"]) == (W, hmax) and o["pull_ok"] == (W <= WMAX)
 
 
+def pull_verdict(g, ring=32):
+    """(pull_ok, orders with a static arrival slot, W) of a recorded day at the default ring horizon."""
+    rc, msg, o = order_tables(g["cost"], g["node2cluster"], int(g["C"]), int(g["tick_minutes"]), [fixture_day(g)], ring=ring)
+    assert rc == 0, msg
+    return o["pull_ok"], o["d_rec"].shape[0], o["W"]
+
+
+def test_slot_corpus_static_arrival_slot_verdicts():
+    """What tests/test_gpu_slot_lengths.py relies on: with 1- and 2-minute slots the day meant for the dense tick has orders with a
+    static arrival slot and yet the verdict is 0 (in-cluster costs spread arrivals over more than DENSE_PULL_WMAX slots): the
+    library picks the dense tick's ring form by itself.  Of the two days beyond slot 32767 the searching one-minute day has the
+    same verdict, the two-minute day with costs // 7 keeps its static arrival slots."""
+    for name in ("slot_0001_0", "slot_0002_0"):
+        ok, m, W = pull_verdict(load_golden(name))
+        assert ok == 0 and m > 0 and W > WMAX, (name, ok, m, W)
+    for name in ("slot_0060_0", "slot_1440_0"):
+        ok, m, W = pull_verdict(load_golden(name))
+        assert ok == 1 and m > 0 and W <= WMAX, (name, ok, m, W)
+    assert pull_verdict(load_golden("slot_long_search"))[0] == 0
+    ok, m, W = pull_verdict(load_golden("slot_long_pull"))
+    assert ok == 1 and 0 < W <= WMAX and m == int(load_golden("slot_long_pull")["order_num"])
+
+
 def _tiny_city():
     g = load_golden("tiny_dispatch")
     return g, g["cost"], g["node2cluster"], int(g["C"])
@@ -206,6 +229,25 @@ def test_edge_days():
     day = (i32(0, 1, 2, 3), i32(0, 1, 2, 0), i32(4, 3, 5, 1))
     assert [order_tables(far, n2c, 2, 10, [day], ring=4, every_order=e)[2]["pull_ok"] for e in (0, 1)] == [1, 0]
     assert order_tables(cost, n2c, 2, 10, [day], ring=4, every_order=1)[2]["pull_ok"] == 1
+
+
+TICK_MINUTES_MAX = (2**31 - 1) // 5          # VDS_TICK_MINUTES_MAX (include/vds.h)
+
+
+def test_days_whose_minutes_do_not_fit_int32_are_refused():
+    """now0 = first release - tick, t * tick and now0 + t * tick for t <= T are int32 on the device (include/vds.h): the builder refuses
+    a day beyond that, and takes the longest slot vds_create accepts on a day that fits."""
+    cost, n2c = _grid()
+    i32 = lambda *x: np.array(x, np.int32)
+    one = (i32(0), i32(1), i32(4))
+    rc, msg, o = order_tables(cost, n2c, 2, TICK_MINUTES_MAX, [one])
+    assert rc == 0 and o["day"].tolist() == [[5, -TICK_MINUTES_MAX, 0, 0]], (rc, msg)
+    for tick, day in ((TICK_MINUTES_MAX + 1, one), (2**30, one),                                 # T * tick
+                      (10, (i32(2**31 - 100, 2**31 - 5), i32(0, 1), i32(1, 2))),                # now0 + T * tick
+                      (TICK_MINUTES_MAX, (i32(0, TICK_MINUTES_MAX), i32(0, 1), i32(1, 2))),         # (six slots of the longest length)
+                      (10, (i32(-2**31 + 5, -2**31 + 9), i32(0, 1), i32(1, 2)))):                 # now0
+        rc, msg, o = order_tables(cost, n2c, 2, tick, [day])
+        assert rc == EINVAL and msg.startswith("vds_load_orders: the day's minutes ") and "do not fit int32" in msg, (tick, rc, msg)
 
 
 def replica_plan(rd, n_days, gran_small=0, regroup=1, alloc=0, cap=None):

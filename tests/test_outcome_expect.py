@@ -6,10 +6,10 @@ SumOrderValue without the value of the order that is never processed."""
 import numpy as np
 import pytest
 
-from helpers import dispatch_by_tick, golden_names, load_golden, make_oracle
+from helpers import dispatch_by_tick, golden_names, load_golden, make_oracle, slot_names
 from outcome_expect import REJECTED, SERVED, VALUE_SUM, WAIT_SUM, expected_from_golden, order_slots, processed_planes, tick_minutes_of
 
-NAMES = golden_names("tiny_") + golden_names("real_")
+NAMES = golden_names("tiny_") + golden_names("real_") + slot_names()
 
 
 def increments(x):

@@ -6,14 +6,14 @@ hold the situations tests/test_gpu_vehicle_outcomes.py relies on."""
 import numpy as np
 import pytest
 
-from helpers import fuzz_names, golden_names, load_golden, recorded_day_facts
+from helpers import fuzz_names, golden_names, load_golden, recorded_day_facts, slot_names
 from outcome_expect import SERVED, VALUE_SUM, WAIT_SUM, order_slots, tick_minutes_of
 from outcome_expect import expected_from_golden as cluster_expectation
 from test_outcome_expect import replay_steps
 from vehicle_outcome_expect import ORDER, PICKUP, VALUE, WAIT, expected_from_golden, processed_rows, slot_sums
 
 TINY = golden_names("tiny_")
-NAMES = TINY + fuzz_names()
+NAMES = TINY + fuzz_names() + slot_names()
 
 
 @pytest.mark.parametrize("name", NAMES)

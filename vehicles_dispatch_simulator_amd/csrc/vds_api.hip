@@ -380,7 +380,8 @@ extern "C" int vds_debug_layout(vds_handle *h, int32_t *out, int32_t cap) {
         ord && S.dense ? S.dense_tab : -1,
     };
     std::copy(w, w + 10, out);
-    for (int i = 10; i < cap; ++i) out[i] = -1;
+    if (cap > 10) out[10] = ord && S.dense ? S.pull : -1;
+    for (int i = 11; i < cap; ++i) out[i] = -1;
     return VDS_OK;
 }
 extern "C" int vds_debug_graph_pool_size() {      // executable graphs kept alive past their handle's use (tests): none any more
@@ -632,6 +633,8 @@ static int create_impl(const vds_config *cfg, vds_handle **out) {
     if (!cfg || !out) return fail(nullptr, VDS_EINVAL, "vds_create: null argument");
     if (cfg->struct_size != (int32_t)sizeof(vds_config)) return fail(nullptr, VDS_EINVAL, "vds_create: vds_config size mismatch (%d vs %zu)", cfg->struct_size, sizeof(vds_config));
     if (cfg->replicas < 1 || cfg->vehicles < 0 || cfg->tick_minutes < 1) return fail(nullptr, VDS_EINVAL, "vds_create: bad replicas/vehicles/tick_minutes");
+    if (cfg->tick_minutes > VDS_TICK_MINUTES_MAX)
+        return fail(nullptr, VDS_EINVAL, "vds_create: tick_minutes %d > %d: the 5 slots of the shortest day would not fit int32 minutes", cfg->tick_minutes, VDS_TICK_MINUTES_MAX);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0) return fail(nullptr, VDS_EHIP, "vds_create: no HIP device available (%s) - libvds has no CPU fallback", hipGetErrorString(e));

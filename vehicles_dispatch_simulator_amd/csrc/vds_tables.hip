@@ -245,6 +245,11 @@ int build_order_tables(const CityView &city, int n_days, const int64_t *day_off,
             const long long end = (long long)rel[O - 1] + 3LL * tick;
             const int T = end >= now0 ? (int)((end - now0) / tick) + 1 : 0;
             if (T > 65535) { day_fail(l, VDS_EINVAL, "vds_load_orders: %lld ticks > 65535 unsupported", T, 0); return; }
+            // minutes are int32 on the device: now0, t * tick and now0 + t * tick for every t <= T (include/vds.h, VDS_TICK_MINUTES_MAX)
+            if (now0 < INT32_MIN || (long long)T * tick > INT32_MAX || now0 + (long long)T * tick > INT32_MAX) {
+                day_fail(l, VDS_EINVAL, "vds_load_orders: the day's minutes %lld .. %lld do not fit int32 (shorter slots or smaller release minutes)", now0, now0 + (long long)T * tick);
+                return;
+            }
             l.O = O; l.T = T; l.now0 = now0;
             H.O = O; H.T = T; H.now0 = (int)now0;
             l.value.resize(O);

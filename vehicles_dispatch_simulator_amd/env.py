@@ -399,10 +399,11 @@ class BatchedDispatchEnv:
     def layout(self) -> Dict[str, int]:
         """The host's layout decision as the handle stands (``vds_debug_layout``; -1 where a value does not apply): ``dense``
         (``k_tick_dense``), ``dense_st`` (its stamp form: neighbour search on the dense layout), ``blk8`` (1 byte cost blocks, 0 int
-        blocks), ``u8_ok``, ``cost8``, ``fast_ok``, ``window_live``, ``seq_pad``, ``dense_lpr``, ``dense_tab``."""
-        out = np.full(10, -1, dtype=np.int32)
+        blocks), ``u8_ok``, ``cost8``, ``fast_ok``, ``window_live``, ``seq_pad``, ``dense_lpr``, ``dense_tab``, ``pull`` (the dense
+        tick's arrivals: 1 static arrival slots, 0 the arrival ring)."""
+        out = np.full(11, -1, dtype=np.int32)
         self._chk(self._lib.vds_debug_layout(self._h, _p(out), int(out.size)))
-        return dict(zip(("dense", "dense_st", "blk8", "u8_ok", "cost8", "fast_ok", "window_live", "seq_pad", "dense_lpr", "dense_tab"),
+        return dict(zip(("dense", "dense_st", "blk8", "u8_ok", "cost8", "fast_ok", "window_live", "seq_pad", "dense_lpr", "dense_tab", "pull"),
                         out.tolist()))
 
     def run_groups(self) -> int:

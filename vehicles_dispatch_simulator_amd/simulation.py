@@ -82,6 +82,16 @@ class _RoadCostMap(object):
         return self.values[:, start]
 
 
+def slot_minutes(TimePeriods):
+    """The slot length in minutes.  The reference works on timestamps and takes any ``TimePeriods``; the engine's slots are whole
+    minutes, and a silent ``// 60`` would run 90-second slots as one-minute slots: anything else is refused."""
+    seconds = pd.Timedelta(TimePeriods).total_seconds()
+    if not (seconds >= 60 and seconds == 60 * int(seconds // 60)):
+        raise ValueError("TimePeriods = %r (%s): slots are whole minutes here, at least one - sub-minute and fractional-minute "
+                         "slots are not supported" % (TimePeriods, pd.Timedelta(TimePeriods)))
+    return int(seconds // 60)
+
+
 class Simulation(object):
     def __init__(self, ClusterMode, DemandPredictionMode, DispatchMode, VehiclesNumber, TimePeriods, LocalRegionBound,
                  SideLengthMeter, VehiclesServiceMeter, NeighborCanServer, FocusOnLocalRegion,
@@ -120,6 +130,7 @@ class Simulation(object):
         self.ClusterMode = ClusterMode
         self.DispatchMode = DispatchMode
         self.VehiclesNumber = VehiclesNumber
+        slot_minutes(TimePeriods)          # (refused here, not at the first load)
         self.TimePeriods = TimePeriods
         self.LocalRegionBound = LocalRegionBound
         self.SideLengthMeter = SideLengthMeter
@@ -258,7 +269,7 @@ class Simulation(object):
         self.Orders = [Order(self, i, self._t0 + pd.Timedelta(minutes=int(rel[i])), int(W.o_pickup[i]), int(W.o_delivery[i]),
                              self._t0 + pd.Timedelta(minutes=int(rel[i])) + PICKUPTIMEWINDOW, int(value[i])) for i in range(rel.size)]
         self._o_value = value.astype(np.int64)
-        self._tick_minutes = int(pd.Timedelta(self.TimePeriods).total_seconds()) // 60
+        self._tick_minutes = slot_minutes(self.TimePeriods)
         # cursor ticks (same rule as libvds: running maximum, last order never processed - quirk Q1)
         tk = np.maximum.accumulate(np.maximum((rel + self._tick_minutes) // self._tick_minutes, 0))
         self._o_tick = tk
