@@ -475,6 +475,41 @@ int vds_read_vehicle_outcomes(vds_handle *h, int32_t *order, int32_t *wait, int3
  * block's address; with replica groups every group has its own nodes. */
 int vds_run_hooked_vehicle_outcomes(vds_handle *h, int32_t on);
 
+/* Per-order results of every replica in ID order - the device form of vds_read_orders: Order.ArriveInfo and Order.PickupWaitTime as
+ * MatchFunction left them (:924-975; what RewardFunction :999-1004 and the end-of-day report :1095-1121 read).  One int32 block
+ * [R][O][2], replicas in the caller's order, O the longest day's order count (the row stride of vds_read_orders); the two words of an
+ * order are one 8-byte piece {vehicle, wait}:
+ *   {Vehicles index >= 0, PickupWaitTime}   a matched order
+ *   {VDS_ORDER_REJECTED, -1}                ArriveInfo == "Reject" (:944, :968)
+ *   {VDS_ORDER_PENDING, -1}                 not processed (yet): its slot was not stepped, the last order of a day (quirk Q1, :914-915),
+ *                                           the padding behind a shorter day's own orders (vds_load_order_days)
+ * Word for word this agrees with vds_read_orders: status 1 / 2 / 0 there is vehicle >= 0 / == -1 / == -2 here, and vehicle and wait
+ * are equal wherever status != 0.
+ * vds_orders_device refreshes, asynchronously on the handle's stream (one kernel), the rows of the orders whose PROCESSING slot lies
+ * in [slot_lo, slot_hi] and returns the block's address (8-byte aligned; dev_ptr may be NULL).  The processed ids of a day are a
+ * prefix of its orders and every slot owns an id-contiguous range, so a slot range is one run of rows per replica.  A replica whose
+ * day has T_r slots is untouched when slot_lo >= T_r; otherwise slot_hi is clamped to T_r - 1, and a range that reaches T_r - 1
+ * extends to the end of the row (the Q1 order and the padding, which read pending).  Orders of the range whose slot was not stepped
+ * yet read pending - all of them when nothing was stepped since the reset.  Rows outside the range keep what the block held (as the
+ * planes that are not requested do in vds_vehicles_device); the block is not cleared when it is made.  (0, INT32_MAX) therefore
+ * writes every element of the block, whatever the memory held; (t, t) after vds_step of slot t is what a per-slot consumer asks for.
+ * The slot's dispatch calls and vds_advance do not change the block.
+ * The block is made on the first call and fixed until vds_load_orders* (its size follows O), a vds_set_replica_days that re-makes
+ * the tables, or vds_destroy.  It is derived on request and not part of a snapshot; `out` is, so after vds_restore a refresh shows
+ * replica r with src_replica[r]'s rows of the snapshot's slot.  No tick, vds_run or vds_run_hooked computes it unless
+ * vds_run_hooked_orders switched it on.  VDS_EINVAL before vds_reset, for slot_lo < 0 and for slot_lo > slot_hi. */
+#define VDS_ORDER_REJECTED (-1)
+#define VDS_ORDER_PENDING  (-2)
+int vds_orders_device(vds_handle *h, int32_t slot_lo, int32_t slot_hi, void **dev_ptr);
+
+/* Sticky switch of vds_run_hooked, like vds_run_hooked_vehicle_outcomes: on != 0 - every slot t of the calls that follow refreshes
+ * range (t, t) of the block of vds_orders_device behind the slot's tick and the other derived blocks and before the policy node, so a
+ * captured policy reads the results of the orders the slot processed (get the address from vds_orders_device before capturing: it is
+ * the one the day uses).  The block accumulates: after a hooked day that followed a full refresh it equals the full refresh of the
+ * finished day.  0 - off, the default: nothing is launched and vds_run_hooked builds node for node the graph it builds without this
+ * switch.  The day graph is keyed by the switch and by the block's address; with replica groups every group has its own nodes. */
+int vds_run_hooked_orders(vds_handle *h, int32_t on);
+
 /* The idle roster: every idle vehicle of every replica in the order a DispatchFunction meets them,
  *     for cluster in self.Clusters:                 # ascending cluster id
  *         for vehicle in cluster.IdleVehicles:      # list order

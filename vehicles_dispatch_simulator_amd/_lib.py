@@ -88,6 +88,8 @@ SYMBOLS = {
     "vds_vehicle_outcomes_device": (C.c_int, [_VP, C.POINTER(_VP)]),
     "vds_read_vehicle_outcomes": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "vds_run_hooked_vehicle_outcomes": (C.c_int, [_VP, _I32]),
+    "vds_orders_device": (C.c_int, [_VP, _I32, _I32, C.POINTER(_VP)]),
+    "vds_run_hooked_orders": (C.c_int, [_VP, _I32]),
     "vds_idle_roster_device": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP)]),
     "vds_read_idle_roster": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "vds_apply_dispatch_roster_device": (C.c_int, [_VP, _VP]),

@@ -96,7 +96,7 @@ enum Mem {
     MEM_STATIC,                          // static tables, scratch, the device copies of Static / State
     MEM_ORDERS,                          // tables of the loaded day (parked by the next vds_load_orders* for its own tables, DevGroup::recycle)
     MEM_MAP,                             // the replica -> day map's device arrays (replaced by vds_set_replica_days / the next load)
-    MEM_RESULTS,                         // per-replica result tables out / arr / slog (sized by S.R)
+    MEM_RESULTS,                         // per-replica result tables out / arr / slog (sized by S.R), with d_orders (sized by R_ext x O: dropped by every order load)
     MEM_STATE,                           // per-replica state (kept across days while the capacities still fit), with d_outc, d_heads, d_veh, d_vout and d_roster
     MEM_IDLE,                            // the idle table alone (regrown by vds_reset / vds_set_idle_cap)
     MEM_SNAP,                            // the snapshot store
@@ -230,6 +230,9 @@ struct vds_handle {
     int *d_vout = nullptr;                   // vds_vehicle_outcomes_device: int32 [R_ext][V][4], made on the first request (in MEM_STATE)
     int hooked_vout = 0;                     // vds_run_hooked_vehicle_outcomes: every slot of vds_run_hooked refreshes d_vout (sticky; 0: off)
     const int *hook_vout = nullptr;          // ... and what the graph at hand was built with (null: off)
+    int *d_orders = nullptr;                 // vds_orders_device: int32 [R_ext][O][2], made on the first request (in MEM_RESULTS, next to `out`)
+    int hooked_orders = 0;                   // vds_run_hooked_orders: every slot t of vds_run_hooked refreshes range (t, t) of d_orders (sticky; 0: off)
+    const int *hook_orders = nullptr;        // ... and what the graph at hand was built with (null: off)
     int *d_roster = nullptr;                 // vds_idle_roster_device: int32 [3][R_ext][V] planes, then int32 [R_ext][C + 1] offsets, made on the first request (in MEM_STATE)
     bool roster_fresh = false;               // the block describes the idle lists as they stand: set by a refresh, cleared by whatever can change a list or re-make the tables
     int hooked_roster = 0;                   // vds_run_hooked_roster: every slot of vds_run_hooked refreshes d_roster (sticky; 0: off)
@@ -916,6 +919,12 @@ static int apply_replica_map(vds_handle *h) {
     return VDS_OK;
 }
 
+// the per-order block of vds_orders_device is sized by R_ext x O: an order load, or a replica map that re-makes the tables, drops it
+static void drop_orders_block(vds_handle *h) {
+    h->mem[MEM_RESULTS].release(h->d_orders);
+    h->d_orders = nullptr;
+}
+
 // per-replica result tables (strided / sized by S.R): out [R][Oq], arr [slots][R] (static arrival slots), slog (hybrid tick)
 static int alloc_results(vds_handle *h) {
     Static &S = h->S;
@@ -932,6 +941,7 @@ static int alloc_results(vds_handle *h) {
     if (h->D.out != nullptr && fits(need_out, h->res_cap_out) && fits(need_arr, h->res_cap_arr) && fits(need_slog, h->res_cap_slog)) return VDS_OK;
     h->mem[MEM_RESULTS].release_all();
     h->D.out = nullptr; h->D.arr = nullptr; h->D.slog = nullptr;
+    h->d_orders = nullptr;                               // (the per-order block lived there: made again on the next request)
     h->res_cap_out = h->res_cap_arr = h->res_cap_slog = 0;
     int rc = dev_alloc(h, MEM_RESULTS, &h->D.out, need_out);
     if (!rc && need_arr) rc = dev_alloc(h, MEM_RESULTS, &h->D.arr, need_arr);
@@ -957,6 +967,7 @@ static int set_replica_days_impl(vds_handle *h, const int32_t *replica_day) {
         // the storage order changed between "as given" and "regrouped by day" (or the padding outgrew the tables): the per-replica
         // tables are strided by S.R - the slow path, allocations
         if ((rc = alloc_state(h, h->alloc_O))) return rc;
+        drop_orders_block(h);
         if ((rc = alloc_results(h))) return rc;
     }
     invalidate(h, GRAPH_TABLES | STATE_MEANING);
@@ -978,6 +989,7 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
         // the state tables stay while their capacities still fit; vds_reset must follow
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->mem[MEM_ORDERS].park();
+        drop_orders_block(h);                 // (its size follows this load's O)
         invalidate(h, GRAPH_TABLES | STATE_MEANING);
         h->have_orders = false; h->have_reset = false;
         clock_reset(h);
@@ -1790,6 +1802,14 @@ static int ensure_outcomes(vds_handle *h) { return ensure_block(h, &h->d_outc, 4
 static int ensure_vehicles(vds_handle *h) { return ensure_block(h, &h->d_veh, std::max<size_t>(6 * (size_t)h->R_ext * h->S.V, 1), 0xFF); }
 static int ensure_vehicle_outcomes(vds_handle *h) { return ensure_block(h, &h->d_vout, std::max<size_t>(4 * (size_t)h->R_ext * h->S.V, 4), -1); }
 
+// (lives with `out`, MEM_RESULTS; not cleared: the first full refresh writes every element)
+static int ensure_orders(vds_handle *h) {
+    if (h->d_orders) return VDS_OK;
+    const int rc = dev_alloc(h, MEM_RESULTS, &h->d_orders, 2 * (size_t)h->R_ext * h->O);
+    if (rc) h->d_orders = nullptr;
+    return rc;
+}
+
 // The two derived blocks that take more than one kernel, for the replicas [r_lo, r_lo + r_n) (r_n <= 0: all), on a stream or as
 // nodes of a day graph.  Every element of a requested plane / of the block is written, whatever the memory held: -1 first, then the scatter.
 // Per-vehicle planes `planes` of d_veh as slot t_last left them (-1: none stepped since the reset)
@@ -1802,6 +1822,18 @@ static void refresh_vehicles(Chain &c, vds_handle *h, int t_last, int planes, in
 static void refresh_vehicle_outcomes(Chain &c, vds_handle *h, int t, int stepped, int r_lo, int r_n) {
     c.add(emit_vehicle_outcomes_fill, h->S, h->d_vout, r_lo, r_n);
     if (stepped && h->S.Oq > 0) c.add(emit_vehicle_outcomes, h->S, h->D, t, stepped, h->d_vout, r_lo, r_n);
+}
+
+// Rows of d_orders of the orders processed in slots [slot_lo, slot_hi]; last: the slot stepped last (-1: none since the reset - the
+// range reads pending).  One kernel; its grid follows the longest id range one replica can have in these slots.
+static void refresh_orders_block(Chain &c, vds_handle *h, int slot_lo, int slot_hi, int last, int r_lo, int r_n) {
+    int tail = 0;                        // a range that reaches a day's last slot runs to the end of the row
+    for (const DayHost &H : h->days)
+        if (slot_lo < H.T && slot_hi >= H.T - 1) tail = std::max(tail, h->O - H.Oq);
+    const long long slots = (long long)std::min(slot_hi, h->S.T - 1) - slot_lo + 1;
+    if (slots <= 0) return;              // every day is over before the range
+    const int ids = (int)std::min<long long>(h->O, slots * h->S.max_tick_orders + tail);
+    c.add(emit_orders_block, h->S, h->D, slot_lo, slot_hi, last, h->O, ids, h->d_orders, r_lo, r_n);
 }
 
 static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
@@ -1819,6 +1851,7 @@ static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int3
         if (h->hooked_veh_planes && (rc = vds_vehicles_device(h, h->hooked_veh_planes, nullptr))) return rc;
         if (h->hooked_vout && (rc = vds_vehicle_outcomes_device(h, nullptr))) return rc;
         if (h->hooked_roster && (rc = vds_idle_roster_device(h, nullptr, nullptr))) return rc;
+        if (h->hooked_orders && (rc = vds_orders_device(h, h->t, h->t, nullptr))) return rc;
         if (policy_graph) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
         if (K > 0 && dev_actions && (rc = vds_apply_dispatch_device(h, K, dev_actions))) return rc;
         if (h->hooked_veh_targets && (rc = vds_apply_dispatch_vehicles_device(h, h->hooked_veh_targets))) return rc;
@@ -1854,6 +1887,9 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
     const bool RO = h->hooked_roster != 0;
     const int *RT = h->S.V > 0 ? (const int *)h->hooked_roster_targets : nullptr;
     if (RO) { const int rcr = ensure_idle_roster(h); if (rcr) return rcr; }
+    // per-order results of the hooked day (vds_run_hooked_orders)
+    const bool OB = h->hooked_orders != 0;
+    if (OB) { const int rcb = ensure_orders(h); if (rcb) return rcb; }
     if (RT && h->S.dense && h->S.V >= (1 << DENSE_ID_BITS))
         return fail(h, VDS_ECAPACITY, "vds_run_hooked: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
     if (VT && h->S.dense && (long long)K + h->S.V >= (1 << DENSE_ID_BITS))
@@ -1872,7 +1908,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                       h->hook_heads == (HL > 0 ? h->d_heads : nullptr) && h->hook_heads_L == HL &&
                       h->hook_veh_planes == VP && h->hook_veh_targets == VT && h->hook_veh == (VP ? h->d_veh : nullptr) &&
                       h->hook_vout == (VO ? h->d_vout : nullptr) &&
-                      h->hook_roster == (RO ? h->d_roster : nullptr) && h->hook_roster_targets == RT;
+                      h->hook_roster == (RO ? h->d_roster : nullptr) && h->hook_roster_targets == RT &&
+                      h->hook_orders == (OB ? h->d_orders : nullptr);
     if (!same) {
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
@@ -1894,6 +1931,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                 if (VO) refresh_vehicle_outcomes(c, h, t, 1, r.lo, r.n);
                 // the group's idle roster as the tick left the lists (vds_run_hooked_roster): one kernel writes every element
                 if (RO) c.add(emit_idle_roster, h->S, h->D, h->d_roster, roster_off(h), r.lo, r.n);
+                // the rows of the orders the group processed in the slot (vds_run_hooked_orders): the block accumulates over the day
+                if (OB) refresh_orders_block(c, h, t, t, t, r.lo, r.n);
             }
             if (policy_graph) {
                 // (the child graph between two EMPTY nodes: with several parents / several children attached to the child-graph node
@@ -1924,7 +1963,8 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
                                 (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr) &&
                                 (h->hook_veh_planes != 0) == (VP != 0) && (h->hook_veh_targets != nullptr) == (VT != nullptr) &&
                                 (h->hook_vout != nullptr) == VO &&
-                                (h->hook_roster != nullptr) == RO && (h->hook_roster_targets != nullptr) == (RT != nullptr);
+                                (h->hook_roster != nullptr) == RO && (h->hook_roster_targets != nullptr) == (RT != nullptr) &&
+                                (h->hook_orders != nullptr) == OB;
         if (!install_graph(h, drop_hook_graph, &h->hook_exec, h->hook_stream, same_shape, g)) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
         h->hook_t0 = h->t; h->hook_n = n_ticks; h->hook_G = G; h->hook_planes = planes; h->hook_K = K; h->hook_actions = dev_actions;
         h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen; h->hook_outc = h->d_outc;
@@ -1932,6 +1972,7 @@ static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32
         h->hook_veh_planes = VP; h->hook_veh_targets = VT; h->hook_veh = VP ? h->d_veh : nullptr;
         h->hook_vout = VO ? h->d_vout : nullptr;
         h->hook_roster = RO ? h->d_roster : nullptr; h->hook_roster_targets = RT;
+        h->hook_orders = OB ? h->d_orders : nullptr;
     }
     HIPCHK(h, hipGraphLaunch(h->hook_exec, h->stream));
     h->t += n_ticks;
@@ -1984,7 +2025,7 @@ int vds_sync(vds_handle *h) {
 // replica map (vds_snapshot.hip).  What is saved: hdr, cnt, idle, ring, ring_min, ring_cnt, fl, both inbox parities, sup, arr, out and the
 // clock (t, last_stepped, the dispatch sequence numbers).  What is not: work / slog / dry (consumed or cleared inside the slot's own
 // launches), err / slow_tick / sup_slot (rewritten by every tick launch; the slot word is set to the restored slot's), the derived
-// blocks (d_obs, d_outc, d_heads, d_veh, d_vout, d_cnt_*: not saved, refreshed on request after a restore - d_vout from `out`, which is saved: replica r then shows the rows of src[r] at the snapshot's slot) and stamp (every stamp is 0xFFFF between API calls: the lists are compact there).
+// blocks (d_obs, d_outc, d_heads, d_veh, d_vout, d_orders, d_cnt_*: not saved, refreshed on request after a restore - d_vout and d_orders from `out`, which is saved: replica r then shows the rows of src[r] at the snapshot's slot) and stamp (every stamp is 0xFFFF between API calls: the lists are compact there).
 static void snap_free(vds_handle *h) {
     vds_handle::Snap &s = h->snap;
     if (!h->mem[MEM_SNAP].empty()) (void)hipStreamSynchronize(h->stream);           // (a copy may still be running)
@@ -2490,6 +2531,31 @@ int vds_run_hooked_roster(vds_handle *h, int32_t on, const void *dev_targets) {
     if (!on && dev_targets) return fail(h, VDS_EINVAL, "vds_run_hooked_roster: roster targets need the roster refreshed in every slot (on != 0)");
     h->hooked_roster = on ? 1 : 0;
     h->hooked_roster_targets = dev_targets;
+    return VDS_OK;
+}
+
+// Per-order results in id order (the device form of vds_read_orders): k_orders_block (vds_orders_block.hip) refreshes, in the int32
+// [R_ext][O][2] block made on the first request, the rows of the orders processed in slots [slot_lo, slot_hi]; every other row keeps
+// what it held.  Derived from `out` on request: nothing of it is saved in a snapshot.
+static int orders_device_impl(vds_handle *h, int32_t slot_lo, int32_t slot_hi, void **dev_ptr) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_orders_device: call vds_reset first");
+    if (slot_lo < 0 || slot_lo > slot_hi) return fail(h, VDS_EINVAL, "vds_orders_device: slots %d .. %d: 0 <= slot_lo <= slot_hi", slot_lo, slot_hi);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int rc = ensure_orders(h);
+    if (rc) return rc;
+    { Chain c(h->stream); refresh_orders_block(c, h, slot_lo, slot_hi, h->last_stepped, 0, 0); }
+    HIPCHK(h, hipGetLastError());
+    if (dev_ptr) *dev_ptr = h->d_orders;
+    return VDS_OK;
+}
+
+int vds_orders_device(vds_handle *h, int32_t slot_lo, int32_t slot_hi, void **dev_ptr) {
+    return guarded(h, "vds_orders_device", [&] { return orders_device_impl(h, slot_lo, slot_hi, dev_ptr); });
+}
+
+int vds_run_hooked_orders(vds_handle *h, int32_t on) {
+    if (!h) return VDS_EINVAL;
+    h->hooked_orders = on ? 1 : 0;
     return VDS_OK;
 }
 

@@ -67,6 +67,11 @@ void emit_vehicle_pull(const Emit &e, const Static &S, const State &D, int t_las
 // the reset.  Two kernels, one launcher each (a graph node each): the -1 fill of the replicas' rows, then the scatter of the slot's orders
 void emit_vehicle_outcomes_fill(const Emit &e, const Static &S, int *blk, int r_lo, int r_n);
 void emit_vehicle_outcomes(const Emit &e, const Static &S, const State &D, int t, int stepped, int *blk, int r_lo, int r_n);
+// ---- vds_orders_block.hip
+// blk: int32 [R_ext][O][2] {vehicle, wait} per order id (8-byte aligned); the rows of the orders processed in slots [slot_lo, slot_hi]
+// (clamped per replica to its own day; the day's last slot takes the rest of the row); last: slot stepped last, -1: none since the
+// reset; ids: the longest id range of one replica (the grid's size).  One kernel
+void emit_orders_block(const Emit &e, const Static &S, const State &D, int slot_lo, int slot_hi, int last, int O, int ids, int *blk, int r_lo, int r_n);
 // ---- vds_dispatch_vehicles.hip: one walk, two forms
 // targets: int32 [R_ext][V] target node per vehicle (negative: stay); seq_base: sequence numbers the slot's earlier dispatch calls used
 void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, int seq_base, int r_lo, int r_n);

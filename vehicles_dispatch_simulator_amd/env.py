@@ -17,6 +17,8 @@ PLANE_OUTCOMES = 32                         # vds_run_hooked plane bit of the pe
 OUTCOME_NAMES = ("served", "rejected", "wait_sum", "value_sum")
 VEHICLE_PLANE_NAMES = ("state", "node", "cluster", "arrive_min", "order", "source")      # planes of vds_vehicles_device, bit k = plane k
 VEHICLE_OUTCOME_NAMES = ("order", "wait", "value", "pickup")      # words of a vehicle's row in the block of vds_vehicle_outcomes_device
+ORDER_REJECTED = -1                         # vehicle word of a rejected order in the block of vds_orders_device (VDS_ORDER_REJECTED)
+ORDER_PENDING = -2                          # ... of an order that was not processed (yet) (VDS_ORDER_PENDING)
 IDLE_ROSTER_NAMES = ("veh", "node", "cluster")                   # planes of the block of vds_idle_roster_device
 
 
@@ -322,7 +324,7 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_run(self._h, int(n_ticks)))
 
     def run_hooked(self, n_ticks: int, actions=None, policy_graph=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False,
-                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None, vehicle_outcomes=False, roster=False, roster_targets=None):
+                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None, vehicle_outcomes=False, roster=False, roster_targets=None, orders=False):
         """``n_ticks`` slots of ``SimCity`` WITH the dispatch hook on the device as one graph launch (``vds_run_hooked``): per slot
         step -> the named observation planes into the block ``obs_torch`` returns (``outcomes=True``: also the slot's per-cluster
         order outcomes into the block ``outcomes_torch`` returns; ``idle_heads=L``: also the first ``L`` entries of every idle list
@@ -344,7 +346,10 @@ class BatchedDispatchEnv:
         ``idle_roster_torch`` returns - capture the policy against those tensors taken before.  ``roster_targets``: the contiguous
         int32 CUDA tensor ``[R, V]`` the policy writes by roster position, applied every slot as ``apply_dispatch_roster_torch``
         behind the policy (``None``: off); it needs ``roster=True`` and excludes ``actions`` and ``vehicle_targets`` - an earlier
-        dispatch of the slot would change the lists the positions refer to.  Both off again by a call without them."""
+        dispatch of the slot would change the lists the positions refer to.  Both off again by a call without them.
+        ``orders=True`` (``vds_run_hooked_orders``): every slot ``t`` also refreshes, before the policy, the rows of the orders it
+        processed in the block ``orders_torch`` returns (range ``(t, t)``); the block accumulates over the day.  Capture the policy
+        against that tensor (or ``orders_device_ptr()``) taken before: the day uses that block.  Off again by a call without it."""
         planes = (1 if idle_pre else 0) | (2 if idle_now else 0) | (4 if supply else 0) | (8 if cl_orders else 0) | (16 if inflight else 0)
         planes |= PLANE_OUTCOMES if outcomes else 0
         K, ptr = 0, None
@@ -362,6 +367,7 @@ class BatchedDispatchEnv:
         vt = None if vehicle_targets is None else self._vehicle_targets_ptr(vehicle_targets, "run_hooked")
         self._chk(self._lib.vds_run_hooked_vehicles(self._h, self._vehicle_mask(vehicle_planes), vt))
         self._chk(self._lib.vds_run_hooked_vehicle_outcomes(self._h, 1 if vehicle_outcomes else 0))
+        self._chk(self._lib.vds_run_hooked_orders(self._h, 1 if orders else 0))
         if roster or roster_targets is not None or self._hooked_roster:
             # (the switch is only touched by a day that uses it, or to switch it off again)
             self._chk(self._lib.vds_run_hooked_roster(self._h, 1 if roster else 0, rt))
@@ -625,6 +631,24 @@ class BatchedDispatchEnv:
         arrs = [np.empty((self.R, self.V), dtype=np.int32) for _ in VEHICLE_OUTCOME_NAMES]
         self._chk(self._lib.vds_read_vehicle_outcomes(self._h, *[_p(a) for a in arrs]))
         return dict(zip(VEHICLE_OUTCOME_NAMES, arrs))
+
+    def orders_device_ptr(self, slot_lo: int = 0, slot_hi: Optional[int] = None) -> int:
+        """Device pointer of the int32 ``[R][O][2]`` block of per-order results in id order (``vds_orders_device``), with the rows of
+        the orders processed in slots ``slot_lo .. slot_hi`` refreshed (``slot_hi=None``: everything from ``slot_lo`` on) and every
+        other row untouched; fixed until the next order load."""
+        p = C.c_void_p()
+        self._chk(self._lib.vds_orders_device(self._h, int(slot_lo), 0x7FFFFFFF if slot_hi is None else int(slot_hi), C.byref(p)))
+        return p.value
+
+    def orders_torch(self, slot_lo: int = 0, slot_hi: Optional[int] = None):
+        """``orders()`` of every replica at once, as a zero-copy ``torch`` int32 tensor ``[R, O, 2]`` on the GPU: row ``i`` of replica
+        ``r`` is ``{vehicle, wait}`` of ``Order.ID == i`` - ``{Vehicles index, PickupWaitTime}`` of a matched order,
+        ``{ORDER_REJECTED, -1}`` of a rejected one, ``{ORDER_PENDING, -1}`` of one not processed (yet).  Only the rows of the orders
+        processed in slots ``slot_lo .. slot_hi`` are refreshed (``slot_hi=None``: everything - the default call writes the whole
+        block); the others keep what they held.  ``orders_torch(t, t)`` after ``step()`` of slot ``t`` is the per-slot form.
+        Asynchronous on the handle's stream; aliases library memory, rewritten by the next call or by ``run_hooked(orders=True)``."""
+        ptr = self.orders_device_ptr(slot_lo, slot_hi)
+        return _device_tensor(ptr, (self.R, self.O, 2), "<i4", self.device)
 
     def idle_roster_device_ptr(self):
         """Device pointers ``(planes, off)`` of the idle roster (``vds_idle_roster_device``), refreshed from the lists as they stand:
