@@ -186,6 +186,41 @@ int vds_reset_again(vds_handle *h);
  * the idle tables are sized from the fullest start list exactly as vds_reset sizes them.  Synchronises like vds_reset. */
 int vds_reset_random(vds_handle *h, const uint64_t *seeds);
 
+/* As vds_reset in every respect - the checks, the first offender reported with its node (read back from the device), the automatic
+ * idle capacity, synchronous, the previous start nodes intact on refusal - with the start nodes read from an int32 [replicas][V]
+ * array ON THE DEVICE: one device-to-device copy on the handle's stream replaces the upload (vds_reset: 41 MB at 1024 x 10k).
+ * The copy is made before anything is re-allocated, so the array may be a view of one of the handle's own blocks: the `node`
+ * plane of vds_vehicles_device starts the next day where the vehicles ended this one.  NULL is VDS_EINVAL, except with V == 0,
+ * where nothing is copied (the rule of vds_apply_dispatch_vehicles_device).  Not capturable. */
+int vds_reset_device(vds_handle *h, const void *dev_veh_init_node);
+
+/* Fleet size per replica.  In the reference the fleet is a constructor argument of each Simulation (VehiclesNumber,
+ * simulator.py:39, :101): `Vehicles = Vehicles[:self.VehiclesNumber]` (:347) keeps the first VehiclesNumber rows of the drivers
+ * file, and InitVehiclesIntoCluster (:249-258) draws one node per such vehicle.  Replica r (the caller's index) behaves like
+ * Simulation(VehiclesNumber = fleet[r]), 0 <= fleet[r] <= V: its vehicles are numbers 0 .. fleet[r] - 1; vehicle v >= fleet[r]
+ * does not exist in that replica - it is in no idle list and no arrival table, never matched, never dispatched, never counted.
+ *   fleet   int32 [replicas], caller's order; NULL = every replica has V vehicles (the default).  A value outside [0, V] is
+ *           VDS_EINVAL, naming the replica.  A map that is V everywhere is kept as "none".
+ * Legal any time after vds_create.  The sizes are a parameter of the resets that follow, not episode state: the call voids the
+ * episode and the snapshot as vds_set_idle_cap does, and vds_reset, vds_reset_random or vds_reset_device must follow -
+ * vds_reset_again right behind it is VDS_EINVAL (the kept lists, the automatic idle capacity and the resident start nodes were
+ * made for other fleets).  The map survives vds_load_orders*, vds_set_replica_days and vds_set_idle_cap.
+ * Resets under a map:
+ *   vds_reset, vds_reset_device   the node array keeps its [replicas][V] shape; entries at v >= fleet[r] are never looked at - they
+ *           may hold anything, -1 included, and are neither checked nor reported as offenders.
+ *   vds_reset_random   replica r draws fleet[r] nodes: the first fleet[r] of the sequence vds_py_random_nodes(seeds[r], N, V, ..)
+ *           yields; "no start nodes found" is judged against fleet[r].
+ *   the automatic idle_cap is sized from the fullest start list of the fleets as they are.
+ * An absent vehicle reads: vds_read_vehicles state 255, the rest -1; vds_vehicles_device -1 in all six planes;
+ * vds_vehicle_outcomes_device a row of -1; the roster's entries from off[r][C] on -1.  A non-negative vehicle-form or roster
+ * target for an absent vehicle is ignored without an error: the vehicle is "not idle".  The sequence numbers of the vehicle form
+ * stay V per call.
+ * After vds_restore through a map replica r has the vehicles of src[r] - the state tables say who exists - while vds_get_fleet keeps
+ * reporting the parameter, which is what the next reset will use. */
+int vds_set_fleet(vds_handle *h, const int32_t *fleet);
+/* fleet: int32 [replicas]; V everywhere when no map is set. */
+int vds_get_fleet(const vds_handle *h, int32_t *fleet);
+
 /* One SimCity iteration up to the Dispatch hook for every replica: UpdateFunction (:1006-1024),
  * MatchFunction (:900-975) incl. FindServerVehicleFunction (:978-996), SupplyExpectFunction
  * (:880-891) and the idle snapshots (:909-910, :1080-1081).  Asynchronous. */
@@ -399,7 +434,7 @@ int vds_run_hooked_idle_heads(vds_handle *h, int32_t L);
  * [6][R][V], plane k at dev_ptr + k*R*V elements, replicas in the caller's order.  Planes 0 .. 4 mean exactly what the fields of
  * vds_read_vehicles mean (state widened to int32), for every replica at once; `planes` is a mask of the VDS_VEH_* bits:
  *   VDS_VEH_STATE   0 idle (in some Cluster.IdleVehicles), 1 on the way with an order, 2 on the way after a dispatch; -1 in
- *                   neither container (cannot happen)
+ *                   neither container (a vehicle beyond the replica's fleet, vds_set_fleet: -1 in all six planes)
  *   VDS_VEH_NODE    idle: LocationNode; on the way: DeliveryPoint - a global node id
  *   VDS_VEH_CLUSTER the cluster whose IdleVehicles / VehiclesArrivetime holds the vehicle (on the way: the destination's cluster -
  *                   the trip origin is not kept on the device, see vds_read_vehicles)

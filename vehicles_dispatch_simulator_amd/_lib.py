@@ -59,6 +59,9 @@ SYMBOLS = {
     "vds_reset": (C.c_int, [_VP, _VP]),
     "vds_reset_again": (C.c_int, [_VP]),
     "vds_reset_random": (C.c_int, [_VP, _VP]),
+    "vds_reset_device": (C.c_int, [_VP, _VP]),
+    "vds_set_fleet": (C.c_int, [_VP, _VP]),
+    "vds_get_fleet": (C.c_int, [_VP, _VP]),
     "vds_step": (C.c_int, [_VP]),
     "vds_apply_dispatch": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP]),
     "vds_apply_dispatch_ex": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),

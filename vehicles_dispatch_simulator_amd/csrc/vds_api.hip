@@ -174,6 +174,10 @@ struct vds_handle {
     unsigned veh_gen = 0, img_veh_gen = 0, img_tables_gen = 0; bool img_valid = false;
     int *d_veh_stage = nullptr;              // vds_reset: the caller's start nodes land here and are checked on the device before they
     unsigned long long *d_bad = nullptr;     // replace d_veh_node (index of the first node outside every cluster, ~0 if none)
+    // vds_set_fleet: vehicles per replica by the caller's index (empty: V everywhere, the kernels get a null pointer); a parameter of
+    // the resets, not episode state.  d_fleet [R_ext] lives in MEM_STATIC: it outlives loads, maps and vds_set_idle_cap
+    std::vector<int> fleet;
+    int *d_fleet = nullptr;
     int *d_obs = nullptr;
     long long *d_outc = nullptr;             // vds_outcomes_device: int64 [4][R_ext][C], made on the first request (in MEM_STATE)
     int *d_heads = nullptr; int heads_L = 0; // vds_idle_heads_device: int32 [2][R_ext][C][heads_L], made on the first request (in MEM_STATE)
@@ -1409,12 +1413,12 @@ static int reset_device(vds_handle *h) {
         if (h->img_valid && h->img_veh_gen == h->veh_gen && h->img_tables_gen == h->tables_gen) {
             launch_reset_image(S, h->D, h->d_reset_img, h->d_reset_base, h->stream);
         } else {
-            launch_reset(S, h->D, h->d_veh_node, h->stream);
+            launch_reset(S, h->D, h->d_veh_node, h->fleet.empty() ? nullptr : h->d_fleet, h->stream);
             launch_reset_capture(S, h->D, h->d_reset_img, h->d_reset_base, h->stream);
             h->img_valid = true; h->img_veh_gen = h->veh_gen; h->img_tables_gen = h->tables_gen;
         }
     } else {
-        launch_reset(S, h->D, h->d_veh_node, h->stream);
+        launch_reset(S, h->D, h->d_veh_node, h->fleet.empty() ? nullptr : h->d_fleet, h->stream);
     }
     HIPCHK(h, hipGetLastError());
     clock_reset(h);
@@ -1455,67 +1459,118 @@ static int ensure_reset_scratch(vds_handle *h) {
     return VDS_OK;
 }
 
-static int reset_impl(vds_handle *h, const int32_t *veh_init_node) {
-    if (!h || !h->have_orders) return fail(h, VDS_EINVAL, "vds_reset: load static tables and orders first");
-    if (!veh_init_node && h->S.V > 0) return fail(h, VDS_EINVAL, "vds_reset: null veh_init_node");
+// vds_set_fleet's map as the kernels take it (null: none) and as the host reads it
+static const int *fleet_dev(const vds_handle *h) { return h->fleet.empty() ? nullptr : h->d_fleet; }
+static int fleet_host(const vds_handle *h, int r) { return fleet_size(h->fleet.empty() ? nullptr : h->fleet.data(), r, h->S.V); }
+// the capacity a reset asks for from the fullest start list
+static int idle_cap_wanted(int V, int fullest) { return std::min(round_up(std::max(V, 1), 64), round_up(2 * fullest + 64, 64)); }
+
+// vds_reset (src: host array) and vds_reset_device (src: device array): only the copy into the staging block differs.  Vehicles at or
+// beyond a replica's fleet (vds_set_fleet) are not looked at, by the checks or by the reset kernels.
+static int reset_impl(vds_handle *h, const char *fn, const void *src, bool src_on_device) {
+    if (!h || !h->have_orders) return fail(h, VDS_EINVAL, "%s: load static tables and orders first", fn);
+    if (!src && h->S.V > 0) return fail(h, VDS_EINVAL, "%s: null veh_init_node", fn);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const Static &S = h->S;
     const size_t n = (size_t)h->R_ext * S.V;
     const bool on_device = S.V > 0 && (size_t)S.C * sizeof(int) <= 60 * 1024 && !(getenv("VDS_RESET_HOST_CHECKS") && getenv("VDS_RESET_HOST_CHECKS")[0] == '1');
+    const int32_t *host_nodes = src_on_device ? nullptr : static_cast<const int32_t *>(src);
+    int rc;
+    if (n > 0 && (on_device || src_on_device)) {
+        // into the staging block first: the nodes of the previous reset stay in place until the new ones have passed, and a device
+        // source is copied before anything is re-allocated (it may be a view of one of the handle's own blocks)
+        if ((rc = ensure_reset_scratch(h))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->d_veh_stage, src, n * sizeof(int), src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    }
+    std::vector<int32_t> read_back;                      // a device source on the host-check path
     if (on_device) {
-        // upload first, then the checks as one kernel over the uploaded array (k_start_nodes_check, vds_random.hip); the nodes of the
-        // previous vds_reset stay in place until the new ones have passed
-        int rc0;
-        if ((rc0 = ensure_reset_scratch(h))) return rc0;
-        HIPCHK(h, hipMemcpyAsync(h->d_veh_stage, veh_init_node, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        // the checks as one kernel over the staged array (k_start_nodes_check, vds_random.hip)
         HIPCHK(h, hipMemsetAsync(h->d_bad, 0xFF, sizeof(unsigned long long), h->stream));
-        launch_start_nodes_check(h->d_veh_stage, h->R_ext, S.N, S.V, S.C, S.node2cluster, h->d_fullest, h->d_bad, h->stream);
+        launch_start_nodes_check(h->d_veh_stage, h->R_ext, S.N, S.V, S.C, S.node2cluster, h->d_fullest, h->d_bad, fleet_dev(h), h->stream);
         HIPCHK(h, hipGetLastError());
         std::vector<int> full((size_t)h->R_ext);
         unsigned long long bad = 0;
         HIPCHK(h, hipMemcpyAsync(full.data(), h->d_fullest, (size_t)h->R_ext * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(&bad, h->d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (bad != ~0ull)
-            return fail(h, VDS_ESTATE, "vds_reset: vehicle %zu starts on node %d which is in no cluster (:254)", (size_t)bad, veh_init_node[bad]);
+        if (bad != ~0ull) {
+            int node = 0;
+            if (host_nodes) node = host_nodes[bad];
+            else HIPCHK(h, hipMemcpy(&node, h->d_veh_stage + bad, sizeof(int), hipMemcpyDeviceToHost));
+            return fail(h, VDS_ESTATE, "%s: vehicle %zu starts on node %d which is in no cluster (:254)", fn, (size_t)bad, node);
+        }
         if (h->cfg.idle_cap <= 0) {
             int fullest = 0;
             for (int r = 0; r < h->R_ext; ++r) fullest = std::max(fullest, full[r]);
-            const int want = std::min(round_up(std::max(S.V, 1), 64), round_up(2 * fullest + 64, 64));
-            if (want > S.idle_cap && (rc0 = set_idle_cap_impl(h, want))) return rc0;
+            const int want = idle_cap_wanted(S.V, fullest);
+            if (want > S.idle_cap && (rc = set_idle_cap_impl(h, want))) return rc;
         }
-        // (a copy, not a pointer swap: d_veh_node belongs to the state tables, which a later vds_load_orders* re-allocates)
-        HIPCHK(h, hipMemcpyAsync(h->d_veh_node, h->d_veh_stage, n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-        h->veh_gen++;
-        if ((rc0 = reset_device(h))) return rc0;
-        return vds_sync(h);
-    }
-    for (size_t i = 0; i < n; ++i) {
-        int node = veh_init_node[i];
-        if (node < 0 || node >= S.N || h->node2cluster[node] < 0)
-            return fail(h, VDS_ESTATE, "vds_reset: vehicle %zu starts on node %d which is in no cluster (:254)", i, node);
-    }
-    if (h->cfg.idle_cap <= 0 && S.V > 0) {
-        // automatic capacity: the fullest start list plus headroom for the day (vehicles concentrate where trips end).
-        // An explicit vds_config.idle_cap is taken as given (overflow is then reported, never silently grown).
-        std::vector<int> cnt((size_t)S.C);
-        int fullest = 0;
-        for (int r = 0; r < h->R_ext; ++r) {
-            std::fill(cnt.begin(), cnt.end(), 0);
-            const int32_t *vn = veh_init_node + (size_t)r * S.V;
-            for (int v = 0; v < S.V; ++v) fullest = std::max(fullest, ++cnt[h->node2cluster[vn[v]]]);
+    } else {
+        if (src_on_device && n > 0) {
+            read_back.resize(n);
+            HIPCHK(h, hipMemcpyAsync(read_back.data(), h->d_veh_stage, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            host_nodes = read_back.data();
         }
-        const int want = std::min(round_up(std::max(S.V, 1), 64), round_up(2 * fullest + 64, 64));
-        if (want > S.idle_cap) {
-            int rc2 = set_idle_cap_impl(h, want);
-            if (rc2) return rc2;
+        for (int r = 0; r < h->R_ext; ++r)
+            for (int v = 0, f = fleet_host(h, r); v < f; ++v) {
+                const size_t i = (size_t)r * S.V + v;
+                const int node = host_nodes[i];
+                if (node < 0 || node >= S.N || h->node2cluster[node] < 0)
+                    return fail(h, VDS_ESTATE, "%s: vehicle %zu starts on node %d which is in no cluster (:254)", fn, i, node);
+            }
+        if (h->cfg.idle_cap <= 0 && S.V > 0) {
+            // automatic capacity: the fullest start list plus headroom for the day (vehicles concentrate where trips end).
+            // An explicit vds_config.idle_cap is taken as given (overflow is then reported, never silently grown).
+            std::vector<int> cnt((size_t)S.C);
+            int fullest = 0;
+            for (int r = 0; r < h->R_ext; ++r) {
+                std::fill(cnt.begin(), cnt.end(), 0);
+                const int32_t *vn = host_nodes + (size_t)r * S.V;
+                for (int v = 0, f = fleet_host(h, r); v < f; ++v) fullest = std::max(fullest, ++cnt[h->node2cluster[vn[v]]]);
+            }
+            const int want = idle_cap_wanted(S.V, fullest);
+            if (want > S.idle_cap && (rc = set_idle_cap_impl(h, want))) return rc;
         }
     }
-    HIPCHK(h, hipMemcpyAsync(h->d_veh_node, veh_init_node, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    // (a copy, not a pointer swap: d_veh_node belongs to the state tables, which a later vds_load_orders* re-allocates)
+    if (on_device || src_on_device) { if (n > 0) HIPCHK(h, hipMemcpyAsync(h->d_veh_node, h->d_veh_stage, n * sizeof(int), hipMemcpyDeviceToDevice, h->stream)); }
+    else HIPCHK(h, hipMemcpyAsync(h->d_veh_node, host_nodes, n * sizeof(int), hipMemcpyHostToDevice, h->stream));
     h->veh_gen++;
-    int rc = reset_device(h);
-    if (rc) return rc;
-    return vds_sync(h);   // veh_init_node is caller-owned: do not retain it; also reports idle_cap overflow
+    if ((rc = reset_device(h))) return rc;
+    return vds_sync(h);   // the caller's array is not retained; also reports idle_cap overflow
+}
+
+static int set_fleet_impl(vds_handle *h, const int32_t *fleet) {
+    if (!h) return fail(h, VDS_EINVAL, "vds_set_fleet: null handle");
+    const int R = h->cfg.replicas, V = h->cfg.vehicles;
+    std::vector<int> next;
+    if (fleet) {
+        bool full = true;
+        for (int r = 0; r < R; ++r) {
+            if (fleet[r] < 0 || fleet[r] > V) return fail(h, VDS_EINVAL, "vds_set_fleet: replica %d: fleet %d outside [0, %d]", r, fleet[r], V);
+            full = full && fleet[r] == V;
+        }
+        if (!full) next.assign(fleet, fleet + R);        // (V everywhere is "none": the default path runs)
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // (a reset that reads the previous map may still be running)
+    if (!next.empty()) {
+        int rc;
+        if (!h->d_fleet && (rc = dev_alloc(h, MEM_STATIC, &h->d_fleet, (size_t)R))) return rc;
+        HIPCHK(h, hipMemcpy(h->d_fleet, next.data(), (size_t)R * sizeof(int), hipMemcpyHostToDevice));
+    }
+    h->fleet.swap(next);
+    // the episode, the snapshot, the kept list image and the resident start nodes were made for the previous fleets
+    invalidate(h, STATE_MEANING);
+    h->have_reset = false; h->nodes_valid = false; h->img_valid = false;
+    return VDS_OK;
+}
+
+static int get_fleet_impl(const vds_handle *h, int32_t *fleet) {
+    if (!h || !fleet) return VDS_EINVAL;
+    for (int r = 0; r < h->cfg.replicas; ++r) fleet[r] = h->fleet.empty() ? h->cfg.vehicles : h->fleet[r];
+    return VDS_OK;
 }
 
 // vds_reset with the start nodes drawn on the device (vds_random.hip): replica r gets the sequence random.Random(seeds[r]) yields
@@ -1526,7 +1581,9 @@ static int reset_random_impl(vds_handle *h, const uint64_t *seeds) {
     const Static &S = h->S;
     bool any = false;
     for (int i = 0; i < S.N && !any; ++i) any = h->node2cluster[i] >= 0;
-    if (!any && S.V > 0) return fail(h, VDS_ESTATE, "vds_reset_random: no node lies in a cluster (:254)");
+    int fleet_max = 0;
+    for (int r = 0; r < h->R_ext; ++r) fleet_max = std::max(fleet_max, fleet_host(h, r));
+    if (!any && fleet_max > 0) return fail(h, VDS_ESTATE, "vds_reset_random: no node lies in a cluster (:254)");
     if ((size_t)(624 + S.C) * sizeof(int) > 64 * 1024) return fail(h, VDS_EINVAL, "vds_reset_random: %d clusters exceed the generator's LDS histogram", S.C);
     if (S.N < 1) return fail(h, VDS_EINVAL, "vds_reset_random: no nodes");
     int rc;
@@ -1534,7 +1591,7 @@ static int reset_random_impl(vds_handle *h, const uint64_t *seeds) {
     if ((rc = ensure_reset_scratch(h))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_seeds, seeds, (size_t)h->R_ext * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     // drawn into the staging array, like vds_reset's upload: the nodes of the previous reset stay in place until these have passed
-    launch_py_random_nodes(h->d_seeds, h->R_ext, S.N, S.V, S.C, S.node2cluster, h->d_veh_stage, h->d_fullest, h->stream);
+    launch_py_random_nodes(h->d_seeds, h->R_ext, S.N, S.V, S.C, S.node2cluster, h->d_veh_stage, h->d_fullest, fleet_dev(h), h->stream);
     HIPCHK(h, hipGetLastError());
     std::vector<int> full((size_t)std::max(h->R_ext, 1));
     HIPCHK(h, hipMemcpyAsync(full.data(), h->d_fullest, (size_t)h->R_ext * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -1545,9 +1602,10 @@ static int reset_random_impl(vds_handle *h, const uint64_t *seeds) {
         fullest = std::max(fullest, full[r]);
     }
     if (h->cfg.idle_cap <= 0 && S.V > 0) {               // automatic capacity, as vds_reset sizes it
-        const int want = std::min(round_up(std::max(S.V, 1), 64), round_up(2 * fullest + 64, 64));
+        const int want = idle_cap_wanted(S.V, fullest);
         if (want > S.idle_cap && (rc = set_idle_cap_impl(h, want))) return rc;
     }
+    // (with fleets the staging block is unwritten behind each one: nothing reads those entries)
     HIPCHK(h, hipMemcpyAsync(h->d_veh_node, h->d_veh_stage, (size_t)h->R_ext * S.V * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
     h->veh_gen++;
     if ((rc = reset_device(h))) return rc;
@@ -3080,8 +3138,18 @@ int vds_replica_ticks(const vds_handle *h, int32_t replica, int32_t *T, int32_t 
 }
 
 int vds_reset(vds_handle *h, const int32_t *veh_init_node) {
-    return guarded(h, "vds_reset", [&] { return reset_impl(h, veh_init_node); });
+    return guarded(h, "vds_reset", [&] { return reset_impl(h, "vds_reset", veh_init_node, false); });
 }
+
+int vds_reset_device(vds_handle *h, const void *dev_veh_init_node) {
+    return guarded(h, "vds_reset_device", [&] { return reset_impl(h, "vds_reset_device", dev_veh_init_node, true); });
+}
+
+int vds_set_fleet(vds_handle *h, const int32_t *fleet) {
+    return guarded(h, "vds_set_fleet", [&] { return set_fleet_impl(h, fleet); });
+}
+
+int vds_get_fleet(const vds_handle *h, int32_t *fleet) { return get_fleet_impl(h, fleet); }
 
 int vds_reset_random(vds_handle *h, const uint64_t *seeds) {
     return guarded(h, "vds_reset_random", [&] { return reset_random_impl(h, seeds); });

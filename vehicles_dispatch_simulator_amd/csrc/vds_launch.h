@@ -1,5 +1,5 @@
-// Host-side launchers of the kernel files, as vds_api.hip calls them: declarations only (included by vds_api.hip and by every file that
-// defines one of them; hashed with the HOST sources: Makefile).
+// Host-side launchers of the kernel files, as vds_api.hip calls them: declarations, and fleet_size (included by vds_api.hip and by
+// every file that defines one of them; hashed with the HOST sources: Makefile).
 //   launch_*  on a stream (the tick files only: the derived blocks and the tensor dispatch forms have no such twin)
 //   emit_*    on a stream or as a kernel node of an explicitly built hipGraph (Emit, vds_device.h), for the replicas
 //             [r_lo, r_lo + r_n) - r_lo a multiple of 16; r_n <= 0 (with r_lo 0): all.  One kernel each: which kernels refresh a
@@ -8,8 +8,14 @@
 #include "vds_device.h"
 
 namespace vds {
+// Fleet size per replica (vds_set_fleet; the reference: VehiclesNumber, simulator.py:101, :347): how many vehicles the caller's
+// replica `ext` has - vehicles 0 .. n - 1, the rest do not exist.  fleet: int32 [R_ext] by the caller's index, null: V everywhere;
+// ext < 0: a padding replica, no vehicles.  The one place the reset kernels and the start-node kernels take their vehicle range from
+// (the only definition in this header: both kernel files include it)
+__host__ __device__ __forceinline__ int fleet_size(const int *fleet, int ext, int V) { return ext < 0 ? 0 : (fleet ? fleet[ext] : V); }
 // ---- vds_tick.hip
-void launch_reset(const Static &S, const State &D, const int *veh_node, hipStream_t st);
+// fleet: see fleet_size (a kernel parameter of its own, not a member of Static: the argument block of the tick kernels stays as it is)
+void launch_reset(const Static &S, const State &D, const int *veh_node, const int *fleet, hipStream_t st);
 bool reset_uses_image(const Static &S);
 void launch_reset_capture(const Static &S, const State &D, unsigned *img, int *base, hipStream_t st);
 void launch_reset_image(const Static &S, const State &D, const unsigned *img, const int *base, hipStream_t st);
@@ -46,10 +52,11 @@ int dfs_walk_pool(const Static &S);
 void set_ablate_dfs(int flags, hipStream_t st);
 void read_prof_dfs(unsigned long long *out, hipStream_t st);
 // ---- vds_random.hip
+// (both by the caller's replica index; fleet: see fleet_size - replica r draws / has checked its first fleet_size vehicles only)
 void launch_py_random_nodes(const unsigned long long *seeds, int R, int N, int V, int C, const int *node2cluster, int *veh_node, int *fullest,
-                            hipStream_t st);
+                            const int *fleet, hipStream_t st);
 void launch_start_nodes_check(const int *veh_node, int R, int N, int V, int C, const int *node2cluster, int *fullest, unsigned long long *bad,
-                              hipStream_t st);
+                              const int *fleet, hipStream_t st);
 // ---- vds_outcomes.hip
 void emit_slot_outcomes(const Emit &e, const Static &S, const State &D, int t, int stepped, long long *oc, int r_lo, int r_n);
 // ---- vds_idle_heads.hip

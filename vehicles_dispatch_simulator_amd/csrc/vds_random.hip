@@ -30,11 +30,12 @@ __device__ __forceinline__ uint32_t rn_temper(uint32_t y) {
 
 __global__ __launch_bounds__(RN_WAVE) void k_py_random_nodes(const unsigned long long *__restrict__ seeds, int N, int V, int C,
                                                              const int *__restrict__ node2cluster, int *__restrict__ veh_node,
-                                                             int *__restrict__ fullest) {
+                                                             int *__restrict__ fullest, const int *__restrict__ fleet) {
     extern __shared__ int rn_lds[];
     uint32_t *mt = reinterpret_cast<uint32_t *>(rn_lds);          // [624]
     int *hist = rn_lds + 624;                                      // [C]
     const int r = blockIdx.x, lane = threadIdx.x;
+    const int nveh = fleet_size(fleet, r, V);                     // the first nveh draws of the sequence; out[nveh ..] stays unwritten
     for (int c = lane; c < C; c += RN_WAVE) hist[c] = 0;
     if (lane == 0) {
         const unsigned long long seed = seeds[r];
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(RN_WAVE) void k_py_random_nodes(const unsigned long
     for (uint32_t n = (uint32_t)N; n; n >>= 1) ++kbits;           // N.bit_length()
     int *out = veh_node + (size_t)r * V;
     int done = 0;
-    for (int tw = 0; done < V && tw < (RN_MAX_TWISTS); ++tw) {
+    for (int tw = 0; done < nveh && tw < (RN_MAX_TWISTS); ++tw) {
         // twist: three sweeps, each 64 words per step
         for (int lo = 0; lo < 624; lo = lo == 0 ? 227 : (lo == 227 ? 454 : 624)) {
             const int hi = lo == 0 ? 227 : (lo == 227 ? 454 : 624);
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(RN_WAVE) void k_py_random_nodes(const unsigned long
             }
         }
         // draws, in index order
-        for (int b = 0; b < 624 && done < V; b += RN_WAVE) {
+        for (int b = 0; b < 624 && done < nveh; b += RN_WAVE) {
             const int i = b + lane;
             bool ok = false;
             int node = 0, cl = -1;
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(RN_WAVE) void k_py_random_nodes(const unsigned long
             }
             const unsigned long long m = __ballot(ok);
             const int pos = done + __popcll(m & ((1ull << lane) - 1ull));
-            if (ok && pos < V) { out[pos] = node; atomicAdd(&hist[cl], 1); }
+            if (ok && pos < nveh) { out[pos] = node; atomicAdd(&hist[cl], 1); }
             done += __popcll(m);
         }
     }
@@ -94,14 +95,15 @@ __global__ __launch_bounds__(RN_WAVE) void k_py_random_nodes(const unsigned long
     int mx = 0;
     for (int c = lane; c < C; c += RN_WAVE) mx = max(mx, hist[c]);
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o, RN_WAVE));
-    if (lane == 0) fullest[r] = done >= V ? mx : -1;
+    if (lane == 0) fullest[r] = done >= nveh ? mx : -1;
 }
 
 // vds_reset's checks of the caller's start nodes on the device, after the upload: every node must lie in a cluster (:254) - the
 // first offender's index is reported - and the fullest start list sizes the idle tables (10^7 nodes: ~8 ms of host loops before)
 #define SC_THREADS 256
 __global__ __launch_bounds__(SC_THREADS) void k_start_nodes_check(const int *__restrict__ veh_node, int N, int V, int C, const int *__restrict__ node2cluster,
-                                                                  int *__restrict__ fullest, unsigned long long *__restrict__ bad) {
+                                                                  int *__restrict__ fullest, unsigned long long *__restrict__ bad,
+                                                                  const int *__restrict__ fleet) {
     extern __shared__ int rn_lds[];
     __shared__ int s_max;
     int *hist = rn_lds;
@@ -110,7 +112,8 @@ __global__ __launch_bounds__(SC_THREADS) void k_start_nodes_check(const int *__r
     if (threadIdx.x == 0) s_max = 0;
     __syncthreads();
     const int *vn = veh_node + (size_t)r * V;
-    for (int v = threadIdx.x; v < V; v += SC_THREADS) {
+    const int nveh = fleet_size(fleet, r, V);                     // (entries behind the fleet: not read, not offenders)
+    for (int v = threadIdx.x; v < nveh; v += SC_THREADS) {
         const int node = vn[v];
         const int cl = (node >= 0 && node < N) ? node2cluster[node] : -1;
         if (cl < 0) atomicMin(bad, (unsigned long long)r * (unsigned long long)V + (unsigned long long)v);
@@ -125,16 +128,17 @@ __global__ __launch_bounds__(SC_THREADS) void k_start_nodes_check(const int *__r
     if (threadIdx.x == 0) fullest[r] = s_max;
 }
 
-void launch_start_nodes_check(const int *veh_node, int R, int N, int V, int C, const int *node2cluster, int *fullest, unsigned long long *bad, hipStream_t st) {
+void launch_start_nodes_check(const int *veh_node, int R, int N, int V, int C, const int *node2cluster, int *fullest, unsigned long long *bad,
+                              const int *fleet, hipStream_t st) {
     if (R <= 0) return;
-    hipLaunchKernelGGL(k_start_nodes_check, dim3(R), dim3(SC_THREADS), (size_t)C * sizeof(int), st, veh_node, N, V, C, node2cluster, fullest, bad);
+    hipLaunchKernelGGL(k_start_nodes_check, dim3(R), dim3(SC_THREADS), (size_t)C * sizeof(int), st, veh_node, N, V, C, node2cluster, fullest, bad, fleet);
 }
 
 void launch_py_random_nodes(const unsigned long long *seeds, int R, int N, int V, int C, const int *node2cluster, int *veh_node, int *fullest,
-                            hipStream_t st) {
+                            const int *fleet, hipStream_t st) {
     if (R <= 0) return;
     const size_t lds = (size_t)(624 + C) * sizeof(int);
-    hipLaunchKernelGGL(k_py_random_nodes, dim3(R), dim3(RN_WAVE), lds, st, seeds, N, V, C, node2cluster, veh_node, fullest);
+    hipLaunchKernelGGL(k_py_random_nodes, dim3(R), dim3(RN_WAVE), lds, st, seeds, N, V, C, node2cluster, veh_node, fullest, fleet);
 }
 
 }  // namespace vds

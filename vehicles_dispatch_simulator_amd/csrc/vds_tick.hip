@@ -48,7 +48,9 @@ __global__ void k_selftest_dpp(const int *in, int *out_wave, int *out_rowmin, in
 
 // ---------------------------------------------------------------------------------------
 // k_reset: wave per (cluster, replica); vehicles are appended in vehicle order (:255-257).
-__global__ __launch_bounds__(256) void k_reset(Static S, State D, const int *veh_node) {
+// All three reset kernels: `fleet` (null: none) is vds_set_fleet's map - a replica's vehicle range ends at fleet_size (vds_launch.h), the
+// first VehiclesNumber rows of the drivers file (:347); the rest of its row of veh_node is not read.
+__global__ __launch_bounds__(256) void k_reset(Static S, State D, const int *veh_node, const int *fleet) {
     const int c = blockIdx.x % S.C;
     const int r = (blockIdx.x / S.C) * 4 + (threadIdx.x >> 6);
     if (r >= S.R) return;
@@ -57,10 +59,11 @@ __global__ __launch_bounds__(256) void k_reset(Static S, State D, const int *veh
     const IdleRef idle = idle_ref(S, D, c, r);
     const int ext = S.int2ext ? S.int2ext[r] : r;          // the caller's replica: its row of start nodes (padding replica: no vehicles)
     const int *vn = veh_node + (size_t)(ext < 0 ? 0 : ext) * S.V;
+    const int nveh = fleet_size(fleet, ext, S.V);
     int count = 0;
-    for (int base = 0; base < (ext < 0 ? 0 : S.V); base += WAVE) {
+    for (int base = 0; base < nveh; base += WAVE) {
         int v = base + lane;
-        int node = v < S.V ? vn[v] : -1;
+        int node = v < nveh ? vn[v] : -1;
         bool mine = node >= 0 && S.node2cluster[node] == c;
         unsigned long long bm = ballot(mine);
         if (mine) {
@@ -83,14 +86,14 @@ __global__ __launch_bounds__(256) void k_reset(Static S, State D, const int *veh
 // each idle list, pass B places the vehicles chunk by chunk (lanes of one cluster are ranked with a
 // ballot).  Needs 16*C ints of LDS; bigger cities use k_reset.
 #define RESET_WAVES 16
-__global__ __launch_bounds__(RESET_WAVES * WAVE) void k_reset_fast(Static S, State D, const int *veh_node) {
+__global__ __launch_bounds__(RESET_WAVES * WAVE) void k_reset_fast(Static S, State D, const int *veh_node, const int *fleet) {
     extern __shared__ int lds_dyn[];
     const int r = blockIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();   // wave-uniform: keep it scalar
     const int C = S.C;
     const int seg = (((S.V + RESET_WAVES - 1) / RESET_WAVES) + WAVE - 1) / WAVE * WAVE;
     const int ext = S.int2ext ? S.int2ext[r] : r;          // the caller's replica: its row of start nodes (padding replica: no vehicles)
-    const int nveh = ext < 0 ? 0 : S.V;
+    const int nveh = fleet_size(fleet, ext, S.V);           // (seg stays a function of V: a full fleet takes the wave ranges it always took)
     const int v0 = min(nveh, wave * seg), v1 = min(nveh, v0 + seg);
     const int *vn = veh_node + (size_t)(ext < 0 ? 0 : ext) * S.V;
     int *mine = lds_dyn + wave * C;
@@ -160,14 +163,14 @@ __global__ __launch_bounds__(RESET_WAVES * WAVE) void k_reset_fast(Static S, Sta
 // the lists then leave as contiguous runs, one wavefront per list.  Needs (RESET_WAVES + 1) C + 1 + V (dense layout: one packed
 // word per vehicle) or + 2 V (wide layout) ints of LDS; cities beyond that keep k_reset_fast.
 template <bool DENSE>
-__global__ __launch_bounds__(RESET_WAVES * WAVE) void k_reset_staged(Static S, State D, const int *veh_node) {
+__global__ __launch_bounds__(RESET_WAVES * WAVE) void k_reset_staged(Static S, State D, const int *veh_node, const int *fleet) {
     extern __shared__ int lds_dyn[];
     const int r = blockIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();
     const int C = S.C;
     const int seg = (((S.V + RESET_WAVES - 1) / RESET_WAVES) + WAVE - 1) / WAVE * WAVE;
     const int ext = S.int2ext ? S.int2ext[r] : r;
-    const int nveh = ext < 0 ? 0 : S.V;
+    const int nveh = fleet_size(fleet, ext, S.V);           // (seg stays a function of V: a full fleet takes the wave ranges it always took)
     const int v0 = min(nveh, wave * seg), v1 = min(nveh, v0 + seg);
     const int *vn = veh_node + (size_t)(ext < 0 ? 0 : ext) * S.V;
     int *mine = lds_dyn + wave * C;
@@ -259,6 +262,7 @@ __global__ __launch_bounds__(RESET_WAVES * WAVE) void k_reset_staged(Static S, S
 // The episode reset of the SAME start nodes (vds_reset_again: what an episode loop calls) does not sort again: k_reset_capture
 // keeps the lists k_reset_fast built as one packed image per replica (entries in list order, `base` = first entry of every
 // cluster), k_reset_image copies it back as runs and clears headers and counters.  Dense layout (one word per entry) only.
+// Both work from the list lengths, which say who exists: fleets per replica (vds_set_fleet) need nothing here.
 #define RESET_IMG_SPLIT 8
 __global__ __launch_bounds__(RESET_WAVES * WAVE) void k_reset_capture(Static S, State D, unsigned *img, int *base) {
     extern __shared__ int lds_dyn[];                    // [C + 1]
@@ -1443,17 +1447,17 @@ void launch_reset_capture(const Static &S, const State &D, unsigned *img, int *b
 void launch_reset_image(const Static &S, const State &D, const unsigned *img, const int *base, hipStream_t st) {
     hipLaunchKernelGGL(k_reset_image, dim3(S.R, RESET_IMG_SPLIT), dim3(RESET_WAVES * WAVE), 0, st, S, D, img, base);
 }
-void launch_reset(const Static &S, const State &D, const int *veh_node, hipStream_t st) {
+void launch_reset(const Static &S, const State &D, const int *veh_node, const int *fleet, hipStream_t st) {
     // the staged form while its LDS image of the lists fits (together with the counters) in 96 KB - configs[0] - [3]
     const size_t staged = ((size_t)(RESET_WAVES + 1) * S.C + 1 + (size_t)(S.dense ? 1 : 2) * S.V) * sizeof(int);
     if (S.C <= 2048 && staged <= (size_t)RESET_STAGED_MAX_LDS && !reset_unstaged()) {
-        if (S.dense) hipLaunchKernelGGL(k_reset_staged<true>, dim3(S.R), dim3(RESET_WAVES * WAVE), staged, st, S, D, veh_node);
-        else hipLaunchKernelGGL(k_reset_staged<false>, dim3(S.R), dim3(RESET_WAVES * WAVE), staged, st, S, D, veh_node);
+        if (S.dense) hipLaunchKernelGGL(k_reset_staged<true>, dim3(S.R), dim3(RESET_WAVES * WAVE), staged, st, S, D, veh_node, fleet);
+        else hipLaunchKernelGGL(k_reset_staged<false>, dim3(S.R), dim3(RESET_WAVES * WAVE), staged, st, S, D, veh_node, fleet);
     } else if (S.C <= 2048) {
-        hipLaunchKernelGGL(k_reset_fast, dim3(S.R), dim3(RESET_WAVES * WAVE), (size_t)RESET_WAVES * S.C * sizeof(int), st, S, D, veh_node);
+        hipLaunchKernelGGL(k_reset_fast, dim3(S.R), dim3(RESET_WAVES * WAVE), (size_t)RESET_WAVES * S.C * sizeof(int), st, S, D, veh_node, fleet);
     } else {
         dim3 grid(S.C * ((S.R + 3) / 4));
-        hipLaunchKernelGGL(k_reset, grid, dim3(256), 0, st, S, D, veh_node);
+        hipLaunchKernelGGL(k_reset, grid, dim3(256), 0, st, S, D, veh_node, fleet);
     }
 }
 

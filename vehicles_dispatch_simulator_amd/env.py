@@ -214,6 +214,37 @@ class BatchedDispatchEnv:
             raise Exception("reset_random: expected %d seeds, got %d" % (self.R, s.size))
         self._chk(self._lib.vds_reset_random(self._h, _p(s)))
 
+    def reset_torch(self, nodes):
+        """``reset`` with the start nodes read from a contiguous int32 CUDA tensor ``[R, V]`` on the handle's device
+        (``vds_reset_device``): the same checks, errors and automatic capacity, one device-to-device copy in place of the upload.
+        The tensor may be a view of the handle's own blocks: ``reset_torch(vehicles_torch(...)["node"])`` starts the next day
+        where the vehicles ended this one.  It must have been produced on (or synchronised with) the handle's stream; it is
+        copied before the call returns.  Entries at or beyond a replica's fleet (``set_fleet``) are not looked at."""
+        self._chk(self._lib.vds_reset_device(self._h, self._vehicle_targets_ptr(nodes, "reset_torch")))
+
+    def set_fleet(self, fleet):
+        """Fleet size per replica (``vds_set_fleet``): replica ``r`` behaves like ``Simulation(VehiclesNumber=fleet[r])`` with
+        vehicles ``0 .. fleet[r] - 1`` (simulator.py:101, :347); ``None``: every replica has ``V`` vehicles again.  A parameter of
+        the resets that follow: the episode and the snapshot are void, ``reset`` / ``reset_random`` / ``reset_torch`` must
+        follow (``reset_again`` is refused)."""
+        if fleet is None:
+            self._chk(self._lib.vds_set_fleet(self._h, None))
+            return
+        f = np.asarray(fleet)
+        if f.ndim != 1 or f.size != self.R or f.dtype.kind not in "iu":
+            raise Exception("set_fleet: expected %d integers (one per replica), got %s %s" % (self.R, f.dtype, list(f.shape)))
+        if f.size and (int(f.min()) < -2**31 or int(f.max()) >= 2**31):
+            raise Exception("set_fleet: a fleet size does not fit int32")
+        f = _i32(f)
+        self._chk(self._lib.vds_set_fleet(self._h, _p(f)))
+
+    @property
+    def fleet(self) -> np.ndarray:
+        """int32 ``[R]``: the fleet sizes the next reset uses (``V`` everywhere when no map is set)."""
+        f = np.empty(self.R, dtype=np.int32)
+        self._chk(self._lib.vds_get_fleet(self._h, _p(f)))
+        return f
+
     def reset_again(self):
         """Restart the episode from the start nodes already resident on the device (asynchronous)."""
         self._chk(self._lib.vds_reset_again(self._h))
