@@ -406,7 +406,7 @@ def test_per_replica_order_days_and_regrouped_storage(kw, maps):
 
 # ---- 6. the hooked day -------------------------------------------------------------------------------------------------------------------------
 # (force_generic = 1: no day graph is built for this tick family - vds_run_hooked goes slot by slot through run_hooked_eager, which
-# refreshes the range through the entry point before it launches the policy)
+# refreshes the range on the stream before it launches the policy)
 @pytest.mark.parametrize("groups,kw", [(1, {}), (2, {}), (1, {"force_generic": 1})], ids=["one-chain", "two-groups", "eager-generic"])
 def test_run_hooked_refreshes_the_slots_rows_for_a_captured_policy(groups, kw):
     """tiny_kmeans at R = 40 with the vehicle-form rule of test_gpu_vehicle_outcomes.hooked_expectation applied by the captured policy,

@@ -382,7 +382,7 @@ def hooked_expectation():
 
 
 # (force_generic = 1: no day graph is built for this tick family - vds_run_hooked goes slot by slot through run_hooked_eager, which
-# refreshes the block through the entry point before it launches the policy)
+# refreshes the block on the stream before it launches the policy)
 @pytest.mark.parametrize("groups,kw", [(1, {}), (2, {}), (1, {"force_generic": 1})], ids=["one-chain", "two-groups", "eager-generic"])
 def test_run_hooked_refreshes_the_block_for_a_captured_policy(groups, kw):
     import torch

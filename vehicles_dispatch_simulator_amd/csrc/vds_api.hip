@@ -4,6 +4,7 @@
 #include "../../include/vds_debug.h"
 #include "vds_device.h"
 #include "vds_launch.h"
+#include "vds_hook_plan.h"
 #include "vds_mem.h"
 #include "vds_tables.h"
 
@@ -218,33 +219,18 @@ struct vds_handle {
     size_t ev_used = 0;
     // vds_run / vds_run_hooked: replica GROUPS, launched one after another in the day graph (run_group_count)
     int run_groups = -1;                     // -1: ask VDS_RUN_GROUPS (default: one)
-    // vds_run_hooked: the hooked day (tick -> observations -> policy -> dispatch per slot) as one executable graph, and what it was built for
+    // vds_run_hooked: the hooked day (tick -> observations -> policy -> dispatch per slot) as one executable graph, the plan it was
+    // built with (vds_hook_plan.h), and the sticky switches of the vds_run_hooked_* setters
     hipGraphExec_t hook_exec = nullptr;
     hipGraphExec_t hook_policy_exec = nullptr;   // (eager fallback: the caller's policy graph instantiated by itself)
     void *hook_policy_inst = nullptr;
-    int hook_t0 = -1, hook_n = 0, hook_G = 1, hook_planes = 0, hook_K = 0;
-    unsigned hook_gen = 0;
-    const long long *hook_outc = nullptr;
+    HookPlan hook_built;
+    HookWant want;
     int *d_veh = nullptr;                    // vds_vehicles_device: int32 [6][R_ext][V], made on the first request (in MEM_STATE)
-    int hooked_heads_L = 0;                  // vds_run_hooked_idle_heads: > 0 - every slot of vds_run_hooked refreshes the heads block (sticky)
-    const int *hook_heads = nullptr; int hook_heads_L = 0;   // ... and what the graph at hand was built with
-    int hooked_veh_planes = 0;               // vds_run_hooked_vehicles: every slot of vds_run_hooked refreshes these planes of d_veh (sticky; 0: none)
-    const void *hooked_veh_targets = nullptr;    // ... and applies this per-vehicle target tensor behind the policy (sticky; null: off)
-    int hook_veh_planes = 0; const void *hook_veh_targets = nullptr; const int *hook_veh = nullptr;   // ... and what the graph at hand was built with
     int *d_vout = nullptr;                   // vds_vehicle_outcomes_device: int32 [R_ext][V][4], made on the first request (in MEM_STATE)
-    int hooked_vout = 0;                     // vds_run_hooked_vehicle_outcomes: every slot of vds_run_hooked refreshes d_vout (sticky; 0: off)
-    const int *hook_vout = nullptr;          // ... and what the graph at hand was built with (null: off)
     int *d_orders = nullptr;                 // vds_orders_device: int32 [R_ext][O][2], made on the first request (in MEM_RESULTS, next to `out`)
-    int hooked_orders = 0;                   // vds_run_hooked_orders: every slot t of vds_run_hooked refreshes range (t, t) of d_orders (sticky; 0: off)
-    const int *hook_orders = nullptr;        // ... and what the graph at hand was built with (null: off)
     int *d_roster = nullptr;                 // vds_idle_roster_device: int32 [3][R_ext][V] planes, then int32 [R_ext][C + 1] offsets, made on the first request (in MEM_STATE)
     bool roster_fresh = false;               // the block describes the idle lists as they stand: set by a refresh, cleared by whatever can change a list or re-make the tables
-    int hooked_roster = 0;                   // vds_run_hooked_roster: every slot of vds_run_hooked refreshes d_roster (sticky; 0: off)
-    const void *hooked_roster_targets = nullptr;     // ... and applies this target tensor by roster position behind the policy (sticky; null: off)
-    const int *hook_roster = nullptr; const void *hook_roster_targets = nullptr;    // ... and what the graph at hand was built with
-    const void *hook_actions = nullptr;
-    void *hook_policy = nullptr;
-    hipStream_t hook_stream = nullptr;
     // vds_snapshot / vds_restore: ONE saved episode state per handle - a store sized like the state and result tables it mirrors, made
     // on the first vds_snapshot (a handle that never takes one allocates nothing), and the host's part of the state: the clock
     unsigned state_gen = 0;                  // bumped wherever the state / result tables are re-made or their meaning changes (another day, another
@@ -397,12 +383,12 @@ extern "C" int vds_debug_graph_pool_size() {      // executable graphs kept aliv
 
 static void drop_hook_graph(vds_handle *h) {
     if (h->hook_exec) {
-        (void)hipStreamSynchronize(h->hook_stream);
+        (void)hipStreamSynchronize((hipStream_t)h->hook_built.stream);
         (void)hipGraphExecDestroy(h->hook_exec);
         h->hook_exec = nullptr;
     }
     if (h->hook_policy_exec) { (void)hipStreamSynchronize(h->stream); (void)hipGraphExecDestroy(h->hook_policy_exec); h->hook_policy_exec = nullptr; h->hook_policy_inst = nullptr; }
-    h->hook_t0 = -1; h->hook_n = 0;
+    h->hook_built = HookPlan();
 }
 
 static void drop_run_graph(vds_handle *h) {
@@ -1894,148 +1880,152 @@ static void refresh_orders_block(Chain &c, vds_handle *h, int slot_lo, int slot_
     c.add(emit_orders_block, h->S, h->D, slot_lo, slot_hi, last, h->O, ids, h->d_orders, r_lo, r_n);
 }
 
-static int run_hooked_eager(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
-    if (policy_graph && h->hook_policy_inst != policy_graph) {
-        if (h->hook_policy_exec) { (void)hipStreamSynchronize(h->stream); (void)hipGraphExecDestroy(h->hook_policy_exec); h->hook_policy_exec = nullptr; }
-        HIPCHK(h, hipGraphInstantiate(&h->hook_policy_exec, (hipGraph_t)policy_graph, nullptr, nullptr, 0));
-        h->hook_policy_inst = policy_graph;
-    }
-    for (int i = 0; i < n_ticks; ++i) {
-        int rc = vds_step(h);
-        if (rc) return rc;
-        if ((planes & 31) && (rc = vds_obs_device_planes(h, planes & 31, nullptr))) return rc;
-        if ((planes & VDS_PLANE_OUTCOMES) && (rc = vds_outcomes_device(h, nullptr))) return rc;
-        if (h->hooked_heads_L > 0 && (rc = vds_idle_heads_device(h, h->hooked_heads_L, nullptr))) return rc;
-        if (h->hooked_veh_planes && (rc = vds_vehicles_device(h, h->hooked_veh_planes, nullptr))) return rc;
-        if (h->hooked_vout && (rc = vds_vehicle_outcomes_device(h, nullptr))) return rc;
-        if (h->hooked_roster && (rc = vds_idle_roster_device(h, nullptr, nullptr))) return rc;
-        if (h->hooked_orders && (rc = vds_orders_device(h, h->t, h->t, nullptr))) return rc;
-        if (policy_graph) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
-        if (K > 0 && dev_actions && (rc = vds_apply_dispatch_device(h, K, dev_actions))) return rc;
-        if (h->hooked_veh_targets && (rc = vds_apply_dispatch_vehicles_device(h, h->hooked_veh_targets))) return rc;
-        if (h->hooked_roster_targets && (rc = vds_apply_dispatch_roster_device(h, h->hooked_roster_targets))) return rc;
-        if ((rc = vds_advance(h))) return rc;
-    }
-    return VDS_OK;
-}
-
-static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
+// What this call of vds_run_hooked does, from its arguments and the sticky switches (h->want: read here and nowhere else): the
+// refusals, then every block the day writes made (ensure_*), then the plan.  n_ticks == 0: an empty plan (n == 0), nothing made.
+// G is the caller's to set (the eager path has no groups).
+static int hook_resolve(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph, HookPlan *plan) {
+    *plan = HookPlan();
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_run_hooked: call vds_reset first");
+    const HookWant &w = h->want;
     if (n_ticks < 0 || planes < 0 || planes > 63 || K < 0 || K > 64 || (K > 0 && !dev_actions))
         return fail(h, VDS_EINVAL, "vds_run_hooked: planes is a mask of the five observation planes and VDS_PLANE_OUTCOMES (0 .. 63), K in [0, 64] with a non-null action tensor");
     if (h->last_stepped == h->t) return fail(h, VDS_EINVAL, "vds_run_hooked: tick %d already stepped; call vds_advance", h->t);
     if (h->t + n_ticks > h->S.T) return fail(h, VDS_EINVAL, "vds_run_hooked: %d slots from slot %d on run past the end of the day (%d slots, :1048)", n_ticks, h->t, h->S.T);
     // roster targets are positions in the lists as the refresh saw them: an earlier dispatch of the slot would change those lists
-    if (h->hooked_roster_targets && (K > 0 || h->hooked_veh_targets))
+    if (w.roster_targets && (K > 0 || w.veh_targets))
         return fail(h, VDS_EINVAL, "vds_run_hooked: roster targets (vds_run_hooked_roster) cannot share a day with K > 0 actions or per-vehicle targets: an earlier dispatch of the slot changes the lists the roster positions refer to");
     if (n_ticks == 0) return VDS_OK;
     h->roster_fresh = false;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (planes & VDS_PLANE_OUTCOMES) { const int rco = ensure_outcomes(h); if (rco) return rco; }
-    const int HL = h->hooked_heads_L;
-    if (HL > 0) { const int rch = ensure_idle_heads(h, HL); if (rch) return rch; }
-    // per-vehicle planes / targets of the hooked day (vds_run_hooked_vehicles); VT's sequence numbers follow the K-form's inside a slot
-    const int VP = h->S.V > 0 ? h->hooked_veh_planes : 0;
-    const int *VT = h->S.V > 0 ? (const int *)h->hooked_veh_targets : nullptr;
-    if (VP) { const int rcv = ensure_vehicles(h); if (rcv) return rcv; }
-    // per-vehicle outcomes of the hooked day (vds_run_hooked_vehicle_outcomes)
-    const bool VO = h->S.V > 0 && h->hooked_vout != 0;
-    if (VO) { const int rcv = ensure_vehicle_outcomes(h); if (rcv) return rcv; }
-    // idle roster / targets by roster position of the hooked day (vds_run_hooked_roster)
-    const bool RO = h->hooked_roster != 0;
-    const int *RT = h->S.V > 0 ? (const int *)h->hooked_roster_targets : nullptr;
-    if (RO) { const int rcr = ensure_idle_roster(h); if (rcr) return rcr; }
-    // per-order results of the hooked day (vds_run_hooked_orders)
-    const bool OB = h->hooked_orders != 0;
-    if (OB) { const int rcb = ensure_orders(h); if (rcb) return rcb; }
-    if (RT && h->S.dense && h->S.V >= (1 << DENSE_ID_BITS))
+    HookPlan p;
+    p.t0 = h->t; p.n = n_ticks; p.planes = planes; p.K = K; p.actions = dev_actions; p.policy = policy_graph;
+    int rc;
+    if (p.outcomes() && (rc = ensure_outcomes(h))) return rc;
+    p.heads_L = w.heads_L;
+    if (p.heads_L > 0 && (rc = ensure_idle_heads(h, p.heads_L))) return rc;
+    // (no vehicles: the per-vehicle blocks and target tensors have nothing in them - off)
+    const bool veh = h->S.V > 0;
+    p.veh_planes = veh ? w.veh_planes : 0;
+    if (p.veh_planes && (rc = ensure_vehicles(h))) return rc;
+    const bool vout = veh && w.vout != 0;
+    if (vout && (rc = ensure_vehicle_outcomes(h))) return rc;
+    if (w.roster && (rc = ensure_idle_roster(h))) return rc;
+    if (w.orders && (rc = ensure_orders(h))) return rc;
+    p.veh_targets = veh ? (const int *)w.veh_targets : nullptr;
+    p.roster_targets = veh ? (const int *)w.roster_targets : nullptr;
+    // (the vehicle form's sequence numbers follow the K-form's inside a slot)
+    if (p.roster_targets && h->S.dense && h->S.V >= (1 << DENSE_ID_BITS))
         return fail(h, VDS_ECAPACITY, "vds_run_hooked: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
-    if (VT && h->S.dense && (long long)K + h->S.V >= (1 << DENSE_ID_BITS))
+    if (p.veh_targets && h->S.dense && (long long)K + h->S.V >= (1 << DENSE_ID_BITS))
         return fail(h, VDS_ECAPACITY, "vds_run_hooked: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
+    // the blocks as they stand now, every ensure_* behind us (another heads_L re-makes d_heads)
+    p.gen = h->tables_gen; p.stream = h->stream;
+    p.outc = h->d_outc;
+    p.heads = p.heads_L > 0 ? h->d_heads : nullptr;
+    p.veh = p.veh_planes ? h->d_veh : nullptr;
+    p.vout = vout ? h->d_vout : nullptr;
+    p.roster = w.roster ? h->d_roster : nullptr;
+    p.orders = w.orders ? h->d_orders : nullptr;
+    *plan = p;
+    return VDS_OK;
+}
+
+// The observation half of slot t for the replicas r, behind their tick: every block the plan has on, in this order
+static void hook_observe(Chain &c, vds_handle *h, const HookPlan &p, int t, int stepped, Rows r) {
+    if (p.obs()) c.add(emit_pack_obs, h->S, h->D, t, stepped, p.obs(), h->d_obs, r.lo, r.n);
+    if (p.outcomes()) c.add(emit_slot_outcomes, h->S, h->D, t, stepped, h->d_outc, r.lo, r.n);
+    if (p.heads_L > 0) c.add(emit_idle_heads, h->S, h->D, p.heads_L, h->d_heads, r.lo, r.n);
+    if (p.veh_planes) refresh_vehicles(c, h, t, p.veh_planes, r.lo, r.n);
+    if (p.vout) refresh_vehicle_outcomes(c, h, t, stepped, r.lo, r.n);
+    if (p.roster) c.add(emit_idle_roster, h->S, h->D, h->d_roster, roster_off(h), r.lo, r.n);      // (one kernel writes every element)
+    if (p.orders) refresh_orders_block(c, h, t, t, t, r.lo, r.n);                                    // (the block accumulates over the day)
+}
+
+// The dispatch half of slot t for the replicas r, one form per call (a slot's K-form nodes of all groups come before its vehicle
+// form's, whose sequence numbers follow theirs; roster targets come alone: hook_resolve)
+enum HookForm { BY_ACTIONS, BY_VEHICLE, BY_ROSTER, HOOK_FORMS };
+static void hook_dispatch(Chain &c, vds_handle *h, const HookPlan &p, int form, int t, Rows r) {
+    if (form == BY_ACTIONS && p.K > 0) c.add(emit_dispatch_dense, h->S, h->D, t, p.K, (const int *)p.actions, 0, r.lo, r.n);
+    if (form == BY_VEHICLE && p.veh_targets) c.add(emit_dispatch_vehicles, h->S, h->D, t, p.veh_targets, p.K, r.lo, r.n);
+    if (form == BY_ROSTER && p.roster_targets) c.add(emit_dispatch_roster, h->S, h->D, t, p.roster_targets, roster_off(h), 0, r.lo, r.n);
+}
+
+// The plan slot by slot on the stream: the observation half as the graph has it, over all replicas; the tick, the dispatch forms and
+// the clock through the public entry points, which own the clock and the per-slot sequence bookkeeping (dispatch_begin).
+static int run_hooked_eager(vds_handle *h, const HookPlan &p) {
+    if (p.policy && h->hook_policy_inst != p.policy) {
+        if (h->hook_policy_exec) { (void)hipStreamSynchronize(h->stream); (void)hipGraphExecDestroy(h->hook_policy_exec); h->hook_policy_exec = nullptr; }
+        HIPCHK(h, hipGraphInstantiate(&h->hook_policy_exec, (hipGraph_t)p.policy, nullptr, nullptr, 0));
+        h->hook_policy_inst = p.policy;
+    }
+    for (int i = 0; i < p.n; ++i) {
+        int rc = vds_step(h);
+        if (rc) return rc;
+        { Chain c(h->stream); hook_observe(c, h, p, h->t, 1, Rows{0, 0}); }
+        HIPCHK(h, hipGetLastError());
+        if (p.roster) h->roster_fresh = true;        // (what vds_apply_dispatch_roster_device asks for)
+        if (p.policy) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
+        if (p.K > 0 && p.actions && (rc = vds_apply_dispatch_device(h, p.K, p.actions))) return rc;
+        if (p.veh_targets && (rc = vds_apply_dispatch_vehicles_device(h, p.veh_targets))) return rc;
+        if (p.roster_targets && (rc = vds_apply_dispatch_roster_device(h, p.roster_targets))) return rc;
+        if ((rc = vds_advance(h))) return rc;
+    }
+    return VDS_OK;
+}
+
+// One call: the plan (hook_resolve), then either the eager loop or the day graph.  The graph at hand is replayed while the plan is
+// the one it was built with (hook_built); another plan builds the slots anew - per slot every group's tick and observation half, the
+// policy, every group's dispatch nodes form by form - and puts them behind hook_exec (install_graph: in place where the shape is the same).
+static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
+    HookPlan plan;
+    const int rcp = hook_resolve(h, n_ticks, planes, K, dev_actions, policy_graph, &plan);
+    if (rcp || plan.n == 0) return rcp;
     const bool groupable = run_groups_hybrid(h) || run_groups_plain(h);
-    if (!run_graph_on(h) || h->profiling || !groupable) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
+    if (!run_graph_on(h) || h->profiling || !groupable) return run_hooked_eager(h, plan);
     { const int rcs = dev_copy_sync(h); if (rcs) return rcs; }
     // replica groups only when the caller asked for them (vds_set_run_groups): measured at configs[1], the
     // hooked day is FASTER as one chain (69.8 / 72.6 / 76.1 us per slot with 1 / 2 / 3 groups, profiles/r05/hooked_groups.txt - the
     // observation and dispatch kernels are chains of dependent loads that gain nothing from running beside a tick, and every group
     // adds two kernel boundaries per slot)
     (void)run_group_count(h);
-    const int G = h->run_groups > 0 ? std::min(run_group_count(h), RUN_GROUPS_MAX) : 1;
-    const bool same = h->hook_exec && h->hook_gen == h->tables_gen && h->hook_t0 == h->t && h->hook_n == n_ticks && h->hook_G == G && h->hook_planes == planes && h->hook_K == K &&
-                      h->hook_actions == dev_actions && h->hook_policy == policy_graph && h->hook_stream == h->stream && h->hook_outc == h->d_outc &&
-                      h->hook_heads == (HL > 0 ? h->d_heads : nullptr) && h->hook_heads_L == HL &&
-                      h->hook_veh_planes == VP && h->hook_veh_targets == VT && h->hook_veh == (VP ? h->d_veh : nullptr) &&
-                      h->hook_vout == (VO ? h->d_vout : nullptr) &&
-                      h->hook_roster == (RO ? h->d_roster : nullptr) && h->hook_roster_targets == RT &&
-                      h->hook_orders == (OB ? h->d_orders : nullptr);
-    if (!same) {
+    plan.G = h->run_groups > 0 ? std::min(run_group_count(h), RUN_GROUPS_MAX) : 1;
+    if (!(h->hook_exec && plan == h->hook_built)) {
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
         Chain c(g);
-        for (int i = 0; i < n_ticks; ++i) {
-            const int t = h->t + i;
-            for (int gi = 0; gi < G; ++gi) {
-                const Rows r = group_rows(h, gi, G);
+        for (int t = plan.t0; t < plan.t0 + plan.n; ++t) {
+            for (int gi = 0; gi < plan.G; ++gi) {
+                const Rows r = group_rows(h, gi, plan.G);
                 if (r.n <= 0) continue;
                 slot_tick(c, h, t, r.lo, r.n, true);        // (stamp form: the hook may look at the lists - packed now)
-                if (planes & 31) c.add(emit_pack_obs, h->S, h->D, t, 1, planes & 31, h->d_obs, r.lo, r.n);
-                // the slot's per-cluster order outcomes, behind the group's last tick launch
-                if (planes & VDS_PLANE_OUTCOMES) c.add(emit_slot_outcomes, h->S, h->D, t, 1, h->d_outc, r.lo, r.n);
-                // the heads of the group's idle lists as the tick left them (vds_run_hooked_idle_heads)
-                if (HL > 0) c.add(emit_idle_heads, h->S, h->D, HL, h->d_heads, r.lo, r.n);
-                // the group's per-vehicle planes as the tick left them (vds_run_hooked_vehicles)
-                if (VP) refresh_vehicles(c, h, t, VP, r.lo, r.n);
-                // what each vehicle of the group earned in the slot (vds_run_hooked_vehicle_outcomes)
-                if (VO) refresh_vehicle_outcomes(c, h, t, 1, r.lo, r.n);
-                // the group's idle roster as the tick left the lists (vds_run_hooked_roster): one kernel writes every element
-                if (RO) c.add(emit_idle_roster, h->S, h->D, h->d_roster, roster_off(h), r.lo, r.n);
-                // the rows of the orders the group processed in the slot (vds_run_hooked_orders): the block accumulates over the day
-                if (OB) refresh_orders_block(c, h, t, t, t, r.lo, r.n);
+                hook_observe(c, h, plan, t, 1, r);
             }
-            if (policy_graph) {
+            if (plan.policy) {
                 // (the child graph between two EMPTY nodes: with several parents / several children attached to the child-graph node
                 // itself the runtime of this image started it after the first parent - actions computed from observations of the slot before)
                 c.add_empty();
-                c.add_child((hipGraph_t)policy_graph);
+                c.add_child((hipGraph_t)plan.policy);
                 c.add_empty();
             }
-            for (int gi = 0; gi < G && K > 0; ++gi) {
-                const Rows r = group_rows(h, gi, G);
-                if (r.n > 0) c.add(emit_dispatch_dense, h->S, h->D, t, K, (const int *)dev_actions, 0, r.lo, r.n);
-            }
-            for (int gi = 0; gi < G && VT; ++gi) {
-                const Rows r = group_rows(h, gi, G);
-                if (r.n > 0) c.add(emit_dispatch_vehicles, h->S, h->D, t, VT, K, r.lo, r.n);
-            }
-            for (int gi = 0; gi < G && RT; ++gi) {
-                const Rows r = group_rows(h, gi, G);
-                if (r.n > 0) c.add(emit_dispatch_roster, h->S, h->D, t, RT, roster_off(h), 0, r.lo, r.n);
-            }
+            for (int form = 0; form < HOOK_FORMS; ++form)
+                for (int gi = 0; gi < plan.G; ++gi) {
+                    const Rows r = group_rows(h, gi, plan.G);
+                    if (r.n > 0) hook_dispatch(c, h, plan, form, t, r);
+                }
         }
         if (c.err != hipSuccess) {
             (void)hipGraphDestroy(g);
             (void)hipGetLastError();
             return fail(h, VDS_EHIP, "vds_run_hooked: building the day graph failed: %s", hipGetErrorString(c.err));
         }
-        const bool same_shape = h->hook_n == n_ticks && h->hook_G == G && ((h->hook_planes & 31) != 0) == ((planes & 31) != 0) && (h->hook_planes & VDS_PLANE_OUTCOMES) == (planes & VDS_PLANE_OUTCOMES) && (h->hook_heads_L > 0) == (HL > 0) &&
-                                (h->hook_K > 0) == (K > 0) && (h->hook_policy != nullptr) == (policy_graph != nullptr) &&
-                                (h->hook_veh_planes != 0) == (VP != 0) && (h->hook_veh_targets != nullptr) == (VT != nullptr) &&
-                                (h->hook_vout != nullptr) == VO &&
-                                (h->hook_roster != nullptr) == RO && (h->hook_roster_targets != nullptr) == (RT != nullptr) &&
-                                (h->hook_orders != nullptr) == OB;
-        if (!install_graph(h, drop_hook_graph, &h->hook_exec, h->hook_stream, same_shape, g)) return run_hooked_eager(h, n_ticks, planes, K, dev_actions, policy_graph);
-        h->hook_t0 = h->t; h->hook_n = n_ticks; h->hook_G = G; h->hook_planes = planes; h->hook_K = K; h->hook_actions = dev_actions;
-        h->hook_policy = policy_graph; h->hook_stream = h->stream; h->hook_gen = h->tables_gen; h->hook_outc = h->d_outc;
-        h->hook_heads = HL > 0 ? h->d_heads : nullptr; h->hook_heads_L = HL;
-        h->hook_veh_planes = VP; h->hook_veh_targets = VT; h->hook_veh = VP ? h->d_veh : nullptr;
-        h->hook_vout = VO ? h->d_vout : nullptr;
-        h->hook_roster = RO ? h->d_roster : nullptr; h->hook_roster_targets = RT;
-        h->hook_orders = OB ? h->d_orders : nullptr;
+        if (!install_graph(h, drop_hook_graph, &h->hook_exec, (hipStream_t)h->hook_built.stream, same_shape(h->hook_built, plan), g)) return run_hooked_eager(h, plan);
+        h->hook_built = plan;
     }
     HIPCHK(h, hipGraphLaunch(h->hook_exec, h->stream));
-    h->t += n_ticks;
+    h->t += plan.n;
     h->last_stepped = h->t - 1;
-    if (K > 0 || VT || RT) { h->dispatch_seq += (K + (VT || RT ? h->S.V : 0)) * n_ticks; h->seq_tick = -1; }
+    const bool by_vehicle = plan.veh_targets || plan.roster_targets;
+    if (plan.K > 0 || by_vehicle) { h->dispatch_seq += (plan.K + (by_vehicle ? h->S.V : 0)) * plan.n; h->seq_tick = -1; }
     return VDS_OK;
 }
 
@@ -2587,8 +2577,8 @@ int vds_read_idle_roster(vds_handle *h, int32_t *veh, int32_t *node, int32_t *cl
 int vds_run_hooked_roster(vds_handle *h, int32_t on, const void *dev_targets) {
     if (!h) return VDS_EINVAL;
     if (!on && dev_targets) return fail(h, VDS_EINVAL, "vds_run_hooked_roster: roster targets need the roster refreshed in every slot (on != 0)");
-    h->hooked_roster = on ? 1 : 0;
-    h->hooked_roster_targets = dev_targets;
+    h->want.roster = on ? 1 : 0;
+    h->want.roster_targets = dev_targets;
     return VDS_OK;
 }
 
@@ -2613,28 +2603,28 @@ int vds_orders_device(vds_handle *h, int32_t slot_lo, int32_t slot_hi, void **de
 
 int vds_run_hooked_orders(vds_handle *h, int32_t on) {
     if (!h) return VDS_EINVAL;
-    h->hooked_orders = on ? 1 : 0;
+    h->want.orders = on ? 1 : 0;
     return VDS_OK;
 }
 
 int vds_run_hooked_vehicle_outcomes(vds_handle *h, int32_t on) {
     if (!h) return VDS_EINVAL;
-    h->hooked_vout = on ? 1 : 0;
+    h->want.vout = on ? 1 : 0;
     return VDS_OK;
 }
 
 int vds_run_hooked_idle_heads(vds_handle *h, int32_t L) {
     if (!h) return VDS_EINVAL;
     if (L < 0 || L > VDS_IDLE_HEADS_MAX) return fail(h, VDS_EINVAL, "vds_run_hooked_idle_heads: L = %d is outside 0 (off) .. %d list positions", L, VDS_IDLE_HEADS_MAX);
-    h->hooked_heads_L = L;
+    h->want.heads_L = L;
     return VDS_OK;
 }
 
 int vds_run_hooked_vehicles(vds_handle *h, int32_t planes, const void *dev_targets) {
     if (!h) return VDS_EINVAL;
     if (planes < 0 || planes > 63) return fail(h, VDS_EINVAL, "vds_run_hooked_vehicles: planes = %d is outside 0 (none) .. 63, a mask of the VDS_VEH_* bits", planes);
-    h->hooked_veh_planes = planes;
-    h->hooked_veh_targets = dev_targets;
+    h->want.veh_planes = planes;
+    h->want.veh_targets = dev_targets;
     return VDS_OK;
 }
 
