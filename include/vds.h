@@ -279,9 +279,38 @@ int vds_apply_dispatch_device(vds_handle *h, int32_t K, const void *dev_actions)
  * Must follow vds_step of the current slot and precede vds_advance (VDS_EINVAL otherwise, and for a NULL tensor - except with V == 0,
  * where the call is a no-op and dev_targets, a tensor without elements, is not looked at).  Asynchronous on
  * the handle's stream, which must be ordered after the producer of the tensor.  A call uses up V dispatch sequence numbers of the
- * slot; on the dense layout VDS_ECAPACITY when the slot's calls would pass 2^25 of them.  Out of scope: a per-vehicle arrive_min /
- * counted as in vds_apply_dispatch_ex. */
+ * slot; on the dense layout VDS_ECAPACITY when the slot's calls would pass 2^25 of them.  The body's own arrival minute and the
+ * counters: vds_apply_dispatch_vehicles_device_ex, of which this call is the (..., NULL, NULL) case. */
 int vds_apply_dispatch_vehicles_device(vds_handle *h, const void *dev_targets);
+
+/* An entry of an arrival-minute tensor that means RealExpTime + RoadCost, as without the tensor; and how far ahead of the slot's
+ * RealExpTime a minute may lie (ceil((minute - now) / tick_minutes) adds tick_minutes - 1 <= INT32_MAX / 5 to the difference: 2^30
+ * plus that stays below 2^31). */
+#define VDS_ARRIVE_ROAD INT32_MIN
+#define VDS_ARRIVE_AHEAD_MAX 1073741824
+
+/* vds_apply_dispatch_vehicles_device with the arrival minute and the counted flag of every move, as vds_apply_dispatch_ex has them
+ * on the host - a DispatchFunction body that writes VehiclesArrivetime itself (a loading delay, its own travel-time model, a
+ * driver's shift: a dispatch to the vehicle's own node that arrives when the shift starts and is no dispatch to the counters):
+ *     for v in self.Vehicles:                       # ascending vehicle number
+ *         n = dev_targets[r][v]
+ *         if n >= 0 and v in v.Cluster.IdleVehicles:
+ *             v.Cluster.IdleVehicles.remove(v)
+ *             Clusters[NodeID2Cluster[n]].VehiclesArrivetime[v] = dev_arrive_min[r][v]     # VDS_ARRIVE_ROAD: RealExpTime + RoadCost
+ *             v.DeliveryPoint = n
+ *             if dev_counted[r][v]:  self.DispatchNum += 1;  self.TotallyDispatchCost += RoadCost(v.LocationNode, n)
+ *   dev_arrive_min  int32 [replicas][V] or NULL (all VDS_ARRIVE_ROAD): the minute on the replica's own day clock, the clock of
+ *                   vds_clock and of the arrive_min plane.  A minute at or before the slot's RealExpTime is legal: the vehicle is back at
+ *                   the next slot's Update (value <= RealExpTime, :1016), and the read side shows the minute as given.  A minute more
+ *                   than VDS_ARRIVE_AHEAD_MAX ahead of RealExpTime is refused like a bad target: the vehicle stays idle where it is,
+ *                   nothing of it is posted, the sticky dispatch error is raised, the other moves are applied.
+ *   dev_counted     int32 [replicas][V] or NULL (all counted): 0 - the move is left out of DispatchNum / TotallyDispatchCost (the body
+ *                   keeps them itself), anything else - counted.  The cost counted is RoadCost whatever the arrival minute.
+ * Only a mover's entries are read: those of a vehicle with a negative target or of one that is not idle may hold anything.
+ * Everything else - call order, V == 0, sequence numbers, dict insertion order, the refusals, the capacity errors - is what
+ * vds_apply_dispatch_vehicles_device documents.  Dispatch runs behind the slot's step: a vehicle cannot be taken off the road
+ * before slot 0's match. */
+int vds_apply_dispatch_vehicles_device_ex(vds_handle *h, const void *dev_targets, const void *dev_arrive_min, const void *dev_counted);
 
 /* `self.step += 1; self.RealExpTime += self.TimePeriods` (:1090-1091). */
 int vds_advance(vds_handle *h);
@@ -472,6 +501,11 @@ int vds_read_vehicles_all(vds_handle *h, int32_t planes, int32_t *out);
  * group has its own nodes.  Never called, or (0, NULL): vds_run_hooked builds exactly the graph it builds without this switch.
  * `planes` outside 0 .. 63: VDS_EINVAL. */
 int vds_run_hooked_vehicles(vds_handle *h, int32_t planes, const void *dev_targets);
+/* ... with the tensors of vds_apply_dispatch_vehicles_device_ex (either may be NULL; vds_run_hooked_vehicles is the (..., NULL, NULL)
+ * case): applied every slot with dev_targets.  VDS_EINVAL with one of them and no dev_targets.  The two addresses are part of the
+ * day graph's key; switching them on or off between two calls builds the slot's dispatch node anew (it is another kernel), other
+ * addresses replace the node's parameters in place.  A day without them builds node for node the graph it builds today. */
+int vds_run_hooked_vehicles_ex(vds_handle *h, int32_t planes, const void *dev_targets, const void *dev_arrive_min, const void *dev_counted);
 
 /* What each vehicle earned in the slot stepped last - the per-vehicle counterpart of vds_outcomes_device: the order MatchFunction
  * (:924-975, neighbour search :978-996 included) gave the vehicle in that slot.  One int32 block [R][V][4], replicas in the caller's
@@ -601,8 +635,26 @@ int vds_read_idle_roster(vds_handle *h, int32_t *veh, int32_t *node, int32_t *cl
  * Must follow vds_step of the current slot and precede vds_advance (VDS_EINVAL otherwise, and for a NULL tensor - except with V == 0,
  * where the call is a no-op and dev_targets is not looked at).  Asynchronous on the handle's stream, which must be ordered after the
  * producer of the tensor.  A call uses up V dispatch sequence numbers of the slot; on the dense layout VDS_ECAPACITY when the slot's
- * calls would pass 2^25 of them.  Out of scope: a per-entry arrive_min / counted as in vds_apply_dispatch_ex. */
+ * calls would pass 2^25 of them.  The body's own arrival minute and the counters: vds_apply_dispatch_roster_device_ex, of which this
+ * call is the (..., NULL, NULL) case. */
 int vds_apply_dispatch_roster_device(vds_handle *h, const void *dev_targets);
+
+/* vds_apply_dispatch_roster_device with the arrival minute and the counted flag of every move, addressed by roster position as the
+ * target is:
+ *     i = 0
+ *     for cluster in self.Clusters:
+ *         for vehicle in cluster.IdleVehicles[:]:
+ *             n = dev_targets[r][i];  a = dev_arrive_min[r][i];  k = dev_counted[r][i];  i += 1
+ *             if n >= 0:
+ *                 cluster.IdleVehicles.remove(vehicle)
+ *                 Clusters[NodeID2Cluster[n]].VehiclesArrivetime[vehicle] = a       # VDS_ARRIVE_ROAD: RealExpTime + RoadCost
+ *                 vehicle.DeliveryPoint = n
+ *                 if k:  self.DispatchNum += 1;  self.TotallyDispatchCost += RoadCost(vehicle.LocationNode, n)
+ * dev_arrive_min / dev_counted: int32 [replicas][V] or NULL, with the sentinel, the past minutes, the VDS_ARRIVE_AHEAD_MAX refusal and
+ * the counters of vds_apply_dispatch_vehicles_device_ex.  Only a mover's entries are read: those of a position with a negative target
+ * and those at or beyond off[r][C] may hold anything.  Freshness, call order, V == 0, sequence numbers, dict insertion order, the
+ * backstop, the refusals and the capacity errors are what vds_apply_dispatch_roster_device documents. */
+int vds_apply_dispatch_roster_device_ex(vds_handle *h, const void *dev_targets, const void *dev_arrive_min, const void *dev_counted);
 
 /* Sticky switch of vds_run_hooked, like vds_run_hooked_vehicles: the idle roster and targets by roster position inside the hooked day.
  *   on           != 0: every slot of the calls that follow refreshes the block of vds_idle_roster_device (one kernel node per replica
@@ -615,6 +667,9 @@ int vds_apply_dispatch_roster_device(vds_handle *h, const void *dev_targets);
  * The day graph is keyed by the switch and by the addresses of the block and of the targets.  Never called, or (0, NULL):
  * vds_run_hooked builds node for node the graph it builds without this switch. */
 int vds_run_hooked_roster(vds_handle *h, int32_t on, const void *dev_targets);
+/* ... with the tensors of vds_apply_dispatch_roster_device_ex (either may be NULL; vds_run_hooked_roster is the (..., NULL, NULL)
+ * case), under the rules of vds_run_hooked_vehicles_ex: VDS_EINVAL with one of them and no dev_targets. */
+int vds_run_hooked_roster_ex(vds_handle *h, int32_t on, const void *dev_targets, const void *dev_arrive_min, const void *dev_counted);
 
 /* Snapshot and restore of the episode state, with per-replica forking (no reference counterpart: a Simulation cannot go back; the
  * nearest thing is Reload + replaying the day, simulator.py:130-212, :1048-1091).

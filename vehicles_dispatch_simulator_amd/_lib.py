@@ -68,6 +68,8 @@ SYMBOLS = {
     "vds_apply_dispatch_device": (C.c_int, [_VP, _I32, _VP]),
     "vds_apply_dispatch_vehicles_device": (C.c_int, [_VP, _VP]),
     "vds_run_hooked_vehicles": (C.c_int, [_VP, _I32, _VP]),
+    "vds_apply_dispatch_vehicles_device_ex": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "vds_run_hooked_vehicles_ex": (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
     "vds_advance": (C.c_int, [_VP]),
     "vds_run": (C.c_int, [_VP, _I32]),
     "vds_set_run_groups": (C.c_int, [_VP, _I32, _I32]),
@@ -97,6 +99,8 @@ SYMBOLS = {
     "vds_read_idle_roster": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "vds_apply_dispatch_roster_device": (C.c_int, [_VP, _VP]),
     "vds_run_hooked_roster": (C.c_int, [_VP, _I32, _VP]),
+    "vds_apply_dispatch_roster_device_ex": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "vds_run_hooked_roster_ex": (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
     "vds_snapshot": (C.c_int, [_VP]),
     "vds_restore": (C.c_int, [_VP, _VP]),
     "vds_restore_device": (C.c_int, [_VP, _VP]),

@@ -142,6 +142,41 @@ static void compare(const Call &a0, const Call &b0) {
     ++g_cases; g_equal += same; g_shape += shape;
 }
 
+// The arrival minutes and counted flags of the two target tensors (vds_run_hooked_vehicles_ex / vds_run_hooked_roster_ex), which the
+// text the plan replaced never had: the rules are written out.  An address alone makes another plan (no stale graph is served); a
+// dispatch node with either tensor is the timed kernel and without both the plain one, so switching them on or off is another shape
+// (the graph is built anew) and another address of a tensor that stays on is the same shape (parameters replaced in place).
+static long long check_times(const HookPlan &base) {
+    CHECK(!base.veh_timed() && !base.roster_timed());
+    long long n = 0;
+    const int *HookPlan::*fields[4] = {&HookPlan::veh_arrive, &HookPlan::veh_counted, &HookPlan::roster_arrive, &HookPlan::roster_counted};
+    for (int i = 0; i < 4; ++i) {
+        HookPlan a = base, b = base;
+        a.*fields[i] = g_int + 30 + i; b.*fields[i] = g_int + 40 + i;
+        CHECK(a != base && base != a && b != base && a != b && a == a);
+        CHECK(!same_shape(base, a) && !same_shape(a, base));                 // on / off: another kernel
+        CHECK(same_shape(a, b) && same_shape(b, a));                         // another address: in place
+        CHECK((i < 2 ? a.veh_timed() : a.roster_timed()) && !(i < 2 ? a.roster_timed() : a.veh_timed()));
+        // the second tensor of the same form on top: still the timed kernel; of the other form: that form's node changes
+        for (int j = 0; j < 4; ++j) {
+            if (j == i) continue;
+            HookPlan c = a;
+            c.*fields[j] = g_int + 50 + j;
+            CHECK(c != a && c != base);
+            CHECK(same_shape(a, c) == (i / 2 == j / 2));
+            ++n;
+        }
+        // every other field still decides as it did
+        HookPlan d = a;
+        d.t0 += 1;
+        CHECK(d != a && same_shape(a, d));
+        d = a; d.n += 1;
+        CHECK(d != a && !same_shape(a, d));
+        n += 8;
+    }
+    return n;
+}
+
 int main() {
     // a day with every block on (the blocks there), and one with every block off (no block made yet)
     const Call on = {4, 2, 2, 31 | VDS_PLANE_OUTCOMES, 3, g_byte + 1, g_byte + 3, g_byte + 5, 7u, 2, 5, g_int + 1, true, true, g_int + 3, true,
@@ -168,6 +203,8 @@ int main() {
     CHECK(!(HookPlan() == plan_of(on)) && !(HookPlan() == plan_of(off)) && !same_shape(HookPlan(), plan_of(on)) && !same_shape(HookPlan(), plan_of(off)));
     // (the cases are not all on one side of either comparison)
     CHECK(g_equal > 0 && g_equal < g_cases && g_shape > g_equal && g_shape < g_cases);
+    const long long nt = check_times(plan_of(ensured(on))) + check_times(plan_of(ensured(off)));
+    printf("hook_plan_check: %lld checks of the arrival-minute / counted addresses\n", nt);
     printf("hook_plan_check: %lld comparisons (%lld equal, %lld of one shape)\n", g_cases, g_equal, g_shape);
     puts("hook_plan_check: ok");
     return 0;

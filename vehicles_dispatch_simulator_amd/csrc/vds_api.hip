@@ -1913,6 +1913,10 @@ static int hook_resolve(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t 
     if (w.orders && (rc = ensure_orders(h))) return rc;
     p.veh_targets = veh ? (const int *)w.veh_targets : nullptr;
     p.roster_targets = veh ? (const int *)w.roster_targets : nullptr;
+    p.veh_arrive = p.veh_targets ? (const int *)w.veh_arrive : nullptr;
+    p.veh_counted = p.veh_targets ? (const int *)w.veh_counted : nullptr;
+    p.roster_arrive = p.roster_targets ? (const int *)w.roster_arrive : nullptr;
+    p.roster_counted = p.roster_targets ? (const int *)w.roster_counted : nullptr;
     // (the vehicle form's sequence numbers follow the K-form's inside a slot)
     if (p.roster_targets && h->S.dense && h->S.V >= (1 << DENSE_ID_BITS))
         return fail(h, VDS_ECAPACITY, "vds_run_hooked: more than 2^%d dispatch actions in one slot (the dense arrival keys carry a %d-bit sequence number); vds_config.force_generic = 5 selects the wide layout", DENSE_ID_BITS, DENSE_ID_BITS);
@@ -1946,8 +1950,8 @@ static void hook_observe(Chain &c, vds_handle *h, const HookPlan &p, int t, int 
 enum HookForm { BY_ACTIONS, BY_VEHICLE, BY_ROSTER, HOOK_FORMS };
 static void hook_dispatch(Chain &c, vds_handle *h, const HookPlan &p, int form, int t, Rows r) {
     if (form == BY_ACTIONS && p.K > 0) c.add(emit_dispatch_dense, h->S, h->D, t, p.K, (const int *)p.actions, 0, r.lo, r.n);
-    if (form == BY_VEHICLE && p.veh_targets) c.add(emit_dispatch_vehicles, h->S, h->D, t, p.veh_targets, p.K, r.lo, r.n);
-    if (form == BY_ROSTER && p.roster_targets) c.add(emit_dispatch_roster, h->S, h->D, t, p.roster_targets, roster_off(h), 0, r.lo, r.n);
+    if (form == BY_VEHICLE && p.veh_targets) c.add(emit_dispatch_vehicles, h->S, h->D, t, p.veh_targets, p.veh_arrive, p.veh_counted, p.K, r.lo, r.n);
+    if (form == BY_ROSTER && p.roster_targets) c.add(emit_dispatch_roster, h->S, h->D, t, p.roster_targets, roster_off(h), p.roster_arrive, p.roster_counted, 0, r.lo, r.n);
 }
 
 // The plan slot by slot on the stream: the observation half as the graph has it, over all replicas; the tick, the dispatch forms and
@@ -1966,8 +1970,8 @@ static int run_hooked_eager(vds_handle *h, const HookPlan &p) {
         if (p.roster) h->roster_fresh = true;        // (what vds_apply_dispatch_roster_device asks for)
         if (p.policy) HIPCHK(h, hipGraphLaunch(h->hook_policy_exec, h->stream));
         if (p.K > 0 && p.actions && (rc = vds_apply_dispatch_device(h, p.K, p.actions))) return rc;
-        if (p.veh_targets && (rc = vds_apply_dispatch_vehicles_device(h, p.veh_targets))) return rc;
-        if (p.roster_targets && (rc = vds_apply_dispatch_roster_device(h, p.roster_targets))) return rc;
+        if (p.veh_targets && (rc = vds_apply_dispatch_vehicles_device_ex(h, p.veh_targets, p.veh_arrive, p.veh_counted))) return rc;
+        if (p.roster_targets && (rc = vds_apply_dispatch_roster_device_ex(h, p.roster_targets, p.roster_arrive, p.roster_counted))) return rc;
         if ((rc = vds_advance(h))) return rc;
     }
     return VDS_OK;
@@ -2574,13 +2578,18 @@ int vds_read_idle_roster(vds_handle *h, int32_t *veh, int32_t *node, int32_t *cl
     return guarded(h, "vds_read_idle_roster", [&] { return read_idle_roster_impl(h, veh, node, cluster, off); });
 }
 
-int vds_run_hooked_roster(vds_handle *h, int32_t on, const void *dev_targets) {
+int vds_run_hooked_roster_ex(vds_handle *h, int32_t on, const void *dev_targets, const void *dev_arrive_min, const void *dev_counted) {
     if (!h) return VDS_EINVAL;
     if (!on && dev_targets) return fail(h, VDS_EINVAL, "vds_run_hooked_roster: roster targets need the roster refreshed in every slot (on != 0)");
+    if (!dev_targets && (dev_arrive_min || dev_counted)) return fail(h, VDS_EINVAL, "vds_run_hooked_roster_ex: arrival minutes / counted flags need the target tensor they belong to");
     h->want.roster = on ? 1 : 0;
     h->want.roster_targets = dev_targets;
+    h->want.roster_arrive = dev_arrive_min;
+    h->want.roster_counted = dev_counted;
     return VDS_OK;
 }
+
+int vds_run_hooked_roster(vds_handle *h, int32_t on, const void *dev_targets) { return vds_run_hooked_roster_ex(h, on, dev_targets, nullptr, nullptr); }
 
 // Per-order results in id order (the device form of vds_read_orders): k_orders_block (vds_orders_block.hip) refreshes, in the int32
 // [R_ext][O][2] block made on the first request, the rows of the orders processed in slots [slot_lo, slot_hi]; every other row keeps
@@ -2620,13 +2629,18 @@ int vds_run_hooked_idle_heads(vds_handle *h, int32_t L) {
     return VDS_OK;
 }
 
-int vds_run_hooked_vehicles(vds_handle *h, int32_t planes, const void *dev_targets) {
+int vds_run_hooked_vehicles_ex(vds_handle *h, int32_t planes, const void *dev_targets, const void *dev_arrive_min, const void *dev_counted) {
     if (!h) return VDS_EINVAL;
     if (planes < 0 || planes > 63) return fail(h, VDS_EINVAL, "vds_run_hooked_vehicles: planes = %d is outside 0 (none) .. 63, a mask of the VDS_VEH_* bits", planes);
+    if (!dev_targets && (dev_arrive_min || dev_counted)) return fail(h, VDS_EINVAL, "vds_run_hooked_vehicles_ex: arrival minutes / counted flags need the target tensor they belong to");
     h->want.veh_planes = planes;
     h->want.veh_targets = dev_targets;
+    h->want.veh_arrive = dev_arrive_min;
+    h->want.veh_counted = dev_counted;
     return VDS_OK;
 }
+
+int vds_run_hooked_vehicles(vds_handle *h, int32_t planes, const void *dev_targets) { return vds_run_hooked_vehicles_ex(h, planes, dev_targets, nullptr, nullptr); }
 
 static int read_counters_impl(vds_handle *h, int64_t *out) {
     if (!h || !h->have_reset || !out) return fail(h, VDS_EINVAL, "vds_read_counters: bad argument / call order");
@@ -3056,13 +3070,14 @@ static int apply_dispatch_device_impl(vds_handle *h, int32_t K, const void *dev_
 // The DispatchFunction body from one target node per vehicle (k_dispatch_vehicles, vds_dispatch_vehicles.hip): sequence number of a
 // vehicle's entry = the numbers the slot's earlier calls used + its vehicle number; the call uses up V of them.
 // (no vehicles: a [replicas][0] tensor has no address, and there is nothing to read from it - n == 0)
-static int apply_dispatch_vehicles_device_impl(vds_handle *h, const void *dev_targets) {
+// arrive / counted (vds_apply_dispatch_vehicles_device_ex; either may be null): the movers' own arrival minutes and counted flags
+static int apply_dispatch_vehicles_device_impl(vds_handle *h, const void *dev_targets, const void *arrive, const void *counted) {
     int seq_base;
     const int rc = dispatch_begin(h, "vds_apply_dispatch_vehicles_device", h ? std::max(h->S.V, 0) : 0, [&] {
         return dev_targets ? VDS_OK : fail(h, VDS_EINVAL, "vds_apply_dispatch_vehicles_device: the target tensor is null");
     }, &seq_base);
     if (rc || seq_base < 0) return rc;
-    Chain(h->stream).add(emit_dispatch_vehicles, h->S, h->D, h->t, (const int *)dev_targets, seq_base, 0, 0);
+    Chain(h->stream).add(emit_dispatch_vehicles, h->S, h->D, h->t, (const int *)dev_targets, (const int *)arrive, (const int *)counted, seq_base, 0, 0);
     HIPCHK(h, hipGetLastError());
     return VDS_OK;
 }
@@ -3070,7 +3085,7 @@ static int apply_dispatch_vehicles_device_impl(vds_handle *h, const void *dev_ta
 // The DispatchFunction body from one target node per ROSTER entry (k_dispatch_roster, vds_dispatch_vehicles.hip): sequence number of
 // an entry = the numbers the slot's earlier calls used + its roster position; the call uses up V of them.  The tensor only means
 // something against the lists the block describes: refused unless the block was refreshed since the last call that can change one.
-static int apply_dispatch_roster_device_impl(vds_handle *h, const void *dev_targets) {
+static int apply_dispatch_roster_device_impl(vds_handle *h, const void *dev_targets, const void *arrive, const void *counted) {
     int seq_base;
     const int rc = dispatch_begin(h, "vds_apply_dispatch_roster_device", h ? std::max(h->S.V, 0) : 0, [&] {
         if (!dev_targets) return fail(h, VDS_EINVAL, "vds_apply_dispatch_roster_device: the target tensor is null");
@@ -3079,7 +3094,7 @@ static int apply_dispatch_roster_device_impl(vds_handle *h, const void *dev_targ
         return VDS_OK;
     }, &seq_base);
     if (rc || seq_base < 0) return rc;
-    Chain(h->stream).add(emit_dispatch_roster, h->S, h->D, h->t, (const int *)dev_targets, roster_off(h), seq_base, 0, 0);
+    Chain(h->stream).add(emit_dispatch_roster, h->S, h->D, h->t, (const int *)dev_targets, roster_off(h), (const int *)arrive, (const int *)counted, seq_base, 0, 0);
     HIPCHK(h, hipGetLastError());
     return VDS_OK;
 }
@@ -3223,12 +3238,16 @@ int vds_apply_dispatch_device(vds_handle *h, int32_t K, const void *dev_actions)
     return guarded(h, "vds_apply_dispatch_device", [&] { return apply_dispatch_device_impl(h, K, dev_actions); });
 }
 
-int vds_apply_dispatch_vehicles_device(vds_handle *h, const void *dev_targets) {
-    return guarded(h, "vds_apply_dispatch_vehicles_device", [&] { return apply_dispatch_vehicles_device_impl(h, dev_targets); });
+int vds_apply_dispatch_vehicles_device_ex(vds_handle *h, const void *dev_targets, const void *dev_arrive_min, const void *dev_counted) {
+    return guarded(h, "vds_apply_dispatch_vehicles_device", [&] { return apply_dispatch_vehicles_device_impl(h, dev_targets, dev_arrive_min, dev_counted); });
 }
 
-int vds_apply_dispatch_roster_device(vds_handle *h, const void *dev_targets) {
-    return guarded(h, "vds_apply_dispatch_roster_device", [&] { return apply_dispatch_roster_device_impl(h, dev_targets); });
+int vds_apply_dispatch_vehicles_device(vds_handle *h, const void *dev_targets) { return vds_apply_dispatch_vehicles_device_ex(h, dev_targets, nullptr, nullptr); }
+
+int vds_apply_dispatch_roster_device_ex(vds_handle *h, const void *dev_targets, const void *dev_arrive_min, const void *dev_counted) {
+    return guarded(h, "vds_apply_dispatch_roster_device", [&] { return apply_dispatch_roster_device_impl(h, dev_targets, dev_arrive_min, dev_counted); });
 }
+
+int vds_apply_dispatch_roster_device(vds_handle *h, const void *dev_targets) { return vds_apply_dispatch_roster_device_ex(h, dev_targets, nullptr, nullptr); }
 
 }  // extern "C"

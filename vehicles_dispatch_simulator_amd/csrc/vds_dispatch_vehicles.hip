@@ -31,6 +31,14 @@
 // read.  (The lists are compact wherever the entry points run the roster form: HDR_RAW == 0, checked in the WKDEBUG build.)
 // Mapping.  State is cluster-major [C][R]: the DV_WAVES wavefronts of a workgroup take consecutive replicas of ONE cluster - their
 // header words, counters and list starts are neighbours.
+// Timed variants (k_dispatch_vehicles_timed / k_dispatch_roster_timed, the *_ex entry points): two more optional tensors int32
+// [R_ext][V], addressed as the target of the form is - arrive (the minute the body wrote into VehiclesArrivetime itself, on the
+// replica's day clock; VDS_ARRIVE_ROAD: now + RoadCost) and counted (0: the move stays out of CNT_DISPATCH / CNT_DISPATCH_COST).  They
+// are a compile-time variant of the walk (Timed / NoTimes): the plain kernels are the instruction streams they were.  Only a mover
+// reads its entries.  A minute at or before `now` is due at the next slot's Update (:1016), compared before anything is subtracted; a
+// minute more than VDS_ARRIVE_AHEAD_MAX ahead (the difference taken in 64 bits) is refused like a bad target.  The entry keeps the
+// minute as given (the read side shows it), so the slots ahead are worked out here and handed to post_slots - post_arrival would
+// subtract `now` from it in 32 bits.  + 4 B per mover and tensor (vehicle form: a gathered 64-byte line each; roster form: contiguous).
 // Byte model: per idle vehicle 4 B of list (8 B on the wide layout) + 4 B of target (vehicle form: a gather, a 64-byte line each;
 // roster form: contiguous, + 8 B of offsets per bucket); per mover the cost gather (a 32-byte sector), node2cluster / node_local
 // (L2) and one arrival post (atomic on ring_cnt + 8 / 16 B entry + 4 B minute on the dense layout) and 4 B of compacted list behind
@@ -39,6 +47,7 @@
 // This file is hashed with the HOST sources (Makefile): it is not one of the tick kernels the profiles/ evidence refers to.
 #include "vds_kernels_common.h"
 #include "vds_launch.h"
+#include "../../include/vds.h"       // VDS_ARRIVE_ROAD, VDS_ARRIVE_AHEAD_MAX
 #ifdef WKDEBUG
 #include <cstdio>
 #endif
@@ -52,12 +61,34 @@ struct ByVehicle {               // tg = targets[ext]
     const int *tg; int V;
     __device__ __forceinline__ int target(int i, bool in, uint2 e) const { return in && e.x < (unsigned)V ? tg[e.x] : -1; }   // (a corrupt entry: never an index)
     __device__ __forceinline__ int id(int i, uint2 e) const { return (int)e.x; }
+    __device__ __forceinline__ int at(int i, uint2 e) const { return (int)e.x; }                // (of a mover: e.x < V)
 };
 struct ByRoster {                // tg = targets[ext] + o0, o0 = off[ext][c]; behind the backstop o0 + i < off[ext][c + 1] <= V
     const int *tg; int o0;
     __device__ __forceinline__ int target(int i, bool in, uint2 e) const { return in ? tg[i] : -1; }
     __device__ __forceinline__ int id(int i, uint2 e) const { return o0 + i; }
+    __device__ __forceinline__ int at(int i, uint2 e) const { return i; }
 };
+
+// The per-entry arrival minute and counted flag of a mover: rows of the two tensors offset as the form's `tg` is, indexed by At::at.
+struct NoTimes { static constexpr bool on = false; };
+struct Timed {
+    static constexpr bool on = true;
+    const int *arrive, *counted;     // either may be null
+};
+
+// post_arrival with the slots ahead (d >= 1) given, not derived from e.z: the ring slot of tick t + d, or the far inbox
+__device__ __forceinline__ void post_slots(const Static &S, const State &D, int dc, int r, int t, int d, int4 e) {
+    if (d < S.H) {
+        ring_post<true>(S, D, dc, r, t + d, e);
+    } else {
+        const size_t db = (size_t)dc * S.R + r;
+        const int np = (t + 1) & 1;
+        const int slot = atomicAdd(&D.hdr[db * HDR_WORDS + HDR_INBOX0 + np], 1);
+        if (slot < S.in_cap) D.inbox[((size_t)np * S.C * S.R + db) * S.in_cap + slot] = e;
+        else atomicOr(&D.err[0], ERR_INBOX_CAP);
+    }
+}
 
 // The bucket (c, r) of this wavefront and the caller's replica `ext` that indexes the tensor; false: none (beyond r_end, or a padding
 // replica: ext -1).  Grid: x = cluster, y = runs of DV_WAVES replicas from S.r_lo on (stored order), up to r_end.
@@ -70,9 +101,9 @@ __device__ __forceinline__ bool dispatch_bucket(const Static &S, int r_end, int 
 }
 
 // The walk over the list of bucket (c, r) - header words hdr, `len` of them idle; seq_base: sequence numbers used up by the slot's
-// earlier dispatch calls.
-template <typename At>
-__device__ __forceinline__ void dispatch_walk(const Static &S, const State &D, int t, int c, int r, int *hdr, int len, int seq_base, const At at) {
+// earlier dispatch calls; tm: the movers' own minutes and flags (NoTimes: now + RoadCost, all counted).
+template <typename At, typename Tm>
+__device__ __forceinline__ void dispatch_walk(const Static &S, const State &D, int t, int c, int r, int *hdr, int len, int seq_base, const At at, const Tm tm) {
     const int lane = lane_id();
     const DayView dvw = day_view(S, r);
     const bool over = t >= dvw.T;                           // the replica's day is over (:1048), its city stands still: targets are refused
@@ -80,11 +111,12 @@ __device__ __forceinline__ void dispatch_walk(const Static &S, const State &D, i
     const IdleRef idle = idle_ref(S, D, c, r);
     const int m = max(min(len, S.idle_cap), 0);            // (never read beyond the table; m <= len)
     const int coff = S.cl_off[c];
-    int newm = 0, nmove = 0;
+    int newm = 0, nmove = 0, ncount = 0;
     long long cost_sum = 0;
     bool bad = false;
     for (int base = 0; base < m; base += WAVE) {
         const int i = base + lane;
+        int arrive = VDS_ARRIVE_ROAD; bool counted = true;   // (timed: a mover's own; declared HERE - further down the plain kernels schedule one s_mov elsewhere)
         const bool in = i < m;
         const uint2 e = in ? idle.get(i) : make_uint2(0u, 0u);
         const int tgt = at.target(i, in, e);
@@ -92,11 +124,26 @@ __device__ __forceinline__ void dispatch_walk(const Static &S, const State &D, i
         bool move = want && !over && tgt < S.N;
         int tc = -1;
         if (move) { tc = S.node2cluster[tgt]; move = tc >= 0; }
+        if constexpr (Tm::on) {
+            if (move) {
+                const int j = at.at(i, e);
+                if (tm.arrive) arrive = tm.arrive[j];
+                if (tm.counted) counted = tm.counted[j] != 0;
+                // (compared before the subtraction, which is taken in 64 bits: no minute overflows it)
+                if (arrive != VDS_ARRIVE_ROAD && arrive > now && (long long)arrive - now > VDS_ARRIVE_AHEAD_MAX) move = false;
+            }
+        }
         bad = bad || (want && !move);
         int cst = 0;
         if (move) {
             cst = S.cost[(size_t)tgt * S.N + coff + e.y];  // RoadCost(LocationNode, target)
-            post_arrival<false, true>(S, D, tc, r, t, now, (int)e.x, seq_base + at.id(i, e), now + cst, 1, S.node_local[tgt]);
+            if constexpr (Tm::on) {
+                const bool road = arrive == VDS_ARRIVE_ROAD;
+                if (road) arrive = now + cst;
+                const int rel = road ? cst : (arrive > now ? arrive - now : 0);
+                post_slots(S, D, tc, r, t, rel <= 0 ? 1 : ticks_until<false>(S, rel),
+                           make_int4((int)e.x, seq_base + at.id(i, e), arrive, meta_pack(t, 1, S.node_local[tgt])));
+            } else post_arrival<false, true>(S, D, tc, r, t, now, (int)e.x, seq_base + at.id(i, e), now + cst, 1, S.node_local[tgt]);
         }
         const bool keep = in && !move;
         const unsigned long long kb = ballot(keep);
@@ -106,7 +153,8 @@ __device__ __forceinline__ void dispatch_walk(const Static &S, const State &D, i
         newm += popc64(kb);
         nmove += popc64(ballot(move));
         // (64-bit sum: the wide layout takes any int32 cost, and 64 of them can pass 2^31)
-        long long cs = move ? (long long)cst : 0ll;
+        long long cs = (Tm::on ? move && counted : move) ? (long long)cst : 0ll;
+        if constexpr (Tm::on) ncount += popc64(ballot(move && counted));
         for (int o = 32; o > 0; o >>= 1) cs += __shfl_xor(cs, o, WAVE);
         cost_sum += cs;
         wave_fence();
@@ -115,21 +163,25 @@ __device__ __forceinline__ void dispatch_walk(const Static &S, const State &D, i
     if (nmove > 0 && lane == 0) {
         hdr[HDR_IDLE] = newm;
         long long *cnt = D.cnt + ((size_t)c * S.R + r) * CNT_WORDS;
-        cnt[CNT_DISPATCH] += nmove;
+        cnt[CNT_DISPATCH] += Tm::on ? ncount : nmove;
         cnt[CNT_DISPATCH_COST] += cost_sum;
     }
 }
 
 // targets: int32 [R_ext][V] by vehicle number
-__global__ __launch_bounds__(DV_WAVES * WAVE) void k_dispatch_vehicles(Static S, State D, int t, int r_end, const int *__restrict__ targets, int seq_base) {
+template <typename Tm>
+__device__ __forceinline__ void dispatch_vehicles_body(const Static &S, const State &D, int t, int r_end, const int *__restrict__ targets, int seq_base, const Tm tm) {
     int c, r, ext;
     if (!dispatch_bucket(S, r_end, c, r, ext)) return;
     int *hdr = D.hdr + ((size_t)c * S.R + r) * HDR_WORDS;
-    dispatch_walk(S, D, t, c, r, hdr, hdr[HDR_IDLE], seq_base, ByVehicle{targets + (size_t)ext * S.V, S.V});
+    const size_t row = (size_t)ext * S.V;
+    if constexpr (Tm::on) dispatch_walk(S, D, t, c, r, hdr, hdr[HDR_IDLE], seq_base, ByVehicle{targets + row, S.V}, Timed{tm.arrive ? tm.arrive + row : nullptr, tm.counted ? tm.counted + row : nullptr});
+    else dispatch_walk(S, D, t, c, r, hdr, hdr[HDR_IDLE], seq_base, ByVehicle{targets + row, S.V}, tm);
 }
 
 // targets: int32 [R_ext][V] by roster position; off: int32 [R_ext][C + 1] of the refresh the tensor was written against
-__global__ __launch_bounds__(DV_WAVES * WAVE) void k_dispatch_roster(Static S, State D, int t, int r_end, const int *__restrict__ targets, const int *__restrict__ off, int seq_base) {
+template <typename Tm>
+__device__ __forceinline__ void dispatch_roster_body(const Static &S, const State &D, int t, int r_end, const int *__restrict__ targets, const int *__restrict__ off, int seq_base, const Tm tm) {
     int c, r, ext;
     if (!dispatch_bucket(S, r_end, c, r, ext)) return;
     int *hdr = D.hdr + ((size_t)c * S.R + r) * HDR_WORDS;
@@ -143,7 +195,23 @@ __global__ __launch_bounds__(DV_WAVES * WAVE) void k_dispatch_roster(Static S, S
         if (lane_id() == 0) atomicOr(&D.err[0], ERR_DISPATCH);
         return;
     }
-    dispatch_walk(S, D, t, c, r, hdr, len, seq_base, ByRoster{targets + (size_t)ext * S.V + o0, o0});
+    const size_t row = (size_t)ext * S.V + o0;
+    if constexpr (Tm::on) dispatch_walk(S, D, t, c, r, hdr, len, seq_base, ByRoster{targets + row, o0}, Timed{tm.arrive ? tm.arrive + row : nullptr, tm.counted ? tm.counted + row : nullptr});
+    else dispatch_walk(S, D, t, c, r, hdr, len, seq_base, ByRoster{targets + row, o0}, tm);
+}
+
+__global__ __launch_bounds__(DV_WAVES * WAVE) void k_dispatch_vehicles(Static S, State D, int t, int r_end, const int *__restrict__ targets, int seq_base) {
+    dispatch_vehicles_body(S, D, t, r_end, targets, seq_base, NoTimes{});
+}
+__global__ __launch_bounds__(DV_WAVES * WAVE) void k_dispatch_roster(Static S, State D, int t, int r_end, const int *__restrict__ targets, const int *__restrict__ off, int seq_base) {
+    dispatch_roster_body(S, D, t, r_end, targets, off, seq_base, NoTimes{});
+}
+// arrive, counted: int32 [R_ext][V] addressed as targets is; either may be null
+__global__ __launch_bounds__(DV_WAVES * WAVE) void k_dispatch_vehicles_timed(Static S, State D, int t, int r_end, const int *__restrict__ targets, const int *__restrict__ arrive, const int *__restrict__ counted, int seq_base) {
+    dispatch_vehicles_body(S, D, t, r_end, targets, seq_base, Timed{arrive, counted});
+}
+__global__ __launch_bounds__(DV_WAVES * WAVE) void k_dispatch_roster_timed(Static S, State D, int t, int r_end, const int *__restrict__ targets, const int *__restrict__ off, const int *__restrict__ arrive, const int *__restrict__ counted, int seq_base) {
+    dispatch_roster_body(S, D, t, r_end, targets, off, seq_base, Timed{arrive, counted});
 }
 
 // one launch of kernel k over the buckets of the replicas [r_lo, r_lo + r_n): args... between r_end and seq_base
@@ -156,12 +224,15 @@ static void emit_dispatch(const Emit &e, K k, const Static &S0, const State &D, 
     emit_kernel(e, k, grid, block, 0, S, D, t, r_lo + n, args..., seq_base);
 }
 
-void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, int seq_base, int r_lo, int r_n) {
-    emit_dispatch(e, k_dispatch_vehicles, S, D, t, seq_base, r_lo, r_n, targets);
+// (arrive / counted both null: the plain kernel)
+void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *arrive, const int *counted, int seq_base, int r_lo, int r_n) {
+    if (arrive || counted) emit_dispatch(e, k_dispatch_vehicles_timed, S, D, t, seq_base, r_lo, r_n, targets, arrive, counted);
+    else emit_dispatch(e, k_dispatch_vehicles, S, D, t, seq_base, r_lo, r_n, targets);
 }
 
-void emit_dispatch_roster(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *off, int seq_base, int r_lo, int r_n) {
-    emit_dispatch(e, k_dispatch_roster, S, D, t, seq_base, r_lo, r_n, targets, off);
+void emit_dispatch_roster(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *off, const int *arrive, const int *counted, int seq_base, int r_lo, int r_n) {
+    if (arrive || counted) emit_dispatch(e, k_dispatch_roster_timed, S, D, t, seq_base, r_lo, r_n, targets, off, arrive, counted);
+    else emit_dispatch(e, k_dispatch_roster, S, D, t, seq_base, r_lo, r_n, targets, off);
 }
 
 }  // namespace vds

@@ -81,9 +81,11 @@ void emit_vehicle_outcomes(const Emit &e, const Static &S, const State &D, int t
 void emit_orders_block(const Emit &e, const Static &S, const State &D, int slot_lo, int slot_hi, int last, int O, int ids, int *blk, int r_lo, int r_n);
 // ---- vds_dispatch_vehicles.hip: one walk, two forms
 // targets: int32 [R_ext][V] target node per vehicle (negative: stay); seq_base: sequence numbers the slot's earlier dispatch calls used
-void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, int seq_base, int r_lo, int r_n);
+// arrive / counted (either may be null; both null: the plain kernels): int32 [R_ext][V] addressed as targets is - the arrival minute
+// (VDS_ARRIVE_ROAD: now + RoadCost) and the counted flag of each mover
+void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *arrive, const int *counted, int seq_base, int r_lo, int r_n);
 // targets: int32 [R_ext][V] target node per roster entry (negative: stay), against the offsets `off` of the refresh it was written for
-void emit_dispatch_roster(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *off, int seq_base, int r_lo, int r_n);
+void emit_dispatch_roster(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *off, const int *arrive, const int *counted, int seq_base, int r_lo, int r_n);
 // ---- vds_idle_roster.hip
 // planes: int32 [3][R_ext][V] {veh, node, cluster} by roster position, off: int32 [R_ext][C + 1]; one kernel writes every element of both
 // (dynamic LDS: idle_roster_lds, (C + 1) ints - C <= IDLE_ROSTER_C_MAX)

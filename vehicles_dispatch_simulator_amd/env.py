@@ -13,6 +13,8 @@ import numpy as np
 from . import _lib
 
 PICKUP_REJECT_THRESHOLD = 600_000_000_000   # int(config/setting.py:7 PICKUPTIMEWINDOW), quirk Q3
+ARRIVE_ROAD = -2 ** 31                      # an arrive_min entry of the device dispatch forms that means now + RoadCost (VDS_ARRIVE_ROAD)
+ARRIVE_AHEAD_MAX = 2 ** 30                  # ... and how far ahead of the slot's minute an entry may lie (VDS_ARRIVE_AHEAD_MAX)
 PLANE_OUTCOMES = 32                         # vds_run_hooked plane bit of the per-cluster order outcomes (VDS_PLANE_OUTCOMES)
 OUTCOME_NAMES = ("served", "rejected", "wait_sum", "value_sum")
 VEHICLE_PLANE_NAMES = ("state", "node", "cluster", "arrive_min", "order", "source")      # planes of vds_vehicles_device, bit k = plane k
@@ -286,6 +288,10 @@ class BatchedDispatchEnv:
             raise Exception("%s: the tensor lives on cuda:%d, the handle on cuda:%d" % (who, targets.device.index, self.device))
         return C.c_void_p(targets.data_ptr())
 
+    def _vehicle_times_ptrs(self, arrive_min, counted, who: str, names=("arrive_min", "counted")):
+        """The two optional ``[R, V]`` tensors that go with a target tensor, checked as the targets are (messages name the argument)."""
+        return [None if x is None else self._vehicle_targets_ptr(x, "%s: %s" % (who, n)) for x, n in zip((arrive_min, counted), names)]
+
     def apply_dispatch_vehicles_torch(self, targets):
         """Per-vehicle dispatch (``vds_apply_dispatch_vehicles_device``): ``targets`` is a contiguous int32 CUDA tensor ``[R, V]`` on
         the handle's device, ``targets[r, v]`` the node vehicle ``v`` of replica ``r`` goes to (negative: stays) - the answer of a
@@ -295,6 +301,19 @@ class BatchedDispatchEnv:
         tensor must stay alive until the handle's stream has passed the call and must have been produced on (or synchronised with)
         that stream - as for ``apply_dispatch_torch``."""
         self._chk(self._lib.vds_apply_dispatch_vehicles_device(self._h, self._vehicle_targets_ptr(targets, "apply_dispatch_vehicles_torch")))
+
+    def apply_dispatch_vehicles_timed_torch(self, targets, arrive_min=None, counted=None):
+        """``apply_dispatch_vehicles_torch`` for a body that writes the arrival minute itself
+        (``vds_apply_dispatch_vehicles_device_ex``).  ``arrive_min`` / ``counted``: contiguous int32 CUDA tensors ``[R, V]`` like
+        ``targets``, or ``None``.  ``arrive_min[r, v]``: the minute vehicle ``v`` arrives, on the replica's own day clock (``clock``,
+        the ``arrive_min`` plane) - ``env.ARRIVE_ROAD`` (and ``None``): now + RoadCost; a minute at or before now: back at the next
+        slot; more than ``2 ** 30`` ahead of now: refused like a bad target.  ``counted[r, v] == 0``: the move is left out of
+        ``DispatchNum`` / ``TotallyDispatchCost`` (``None``: all counted).  Only a mover's entries are read.  Per replica it is
+        ``oracle.dispatch_at([v], [targets[r, v]], [arrive_min[r, v]], counted[r, v])`` for every idle ``v`` with a target, in
+        ascending vehicle number.  Dispatch runs behind the slot's step: nothing leaves before slot 0's match."""
+        who = "apply_dispatch_vehicles_timed_torch"
+        am, ct = self._vehicle_times_ptrs(arrive_min, counted, who)
+        self._chk(self._lib.vds_apply_dispatch_vehicles_device_ex(self._h, self._vehicle_targets_ptr(targets, who), am, ct))
 
     def apply_dispatch_roster_torch(self, targets):
         """Dispatch by roster position (``vds_apply_dispatch_roster_device``): ``targets`` is a contiguous int32 CUDA tensor ``[R, V]`` on
@@ -306,6 +325,15 @@ class BatchedDispatchEnv:
         over is skipped and raises once at the next ``sync`` / read.  Asynchronous, no host copy; the tensor must stay alive until the
         handle's stream has passed the call and must have been produced on (or synchronised with) that stream."""
         self._chk(self._lib.vds_apply_dispatch_roster_device(self._h, self._vehicle_targets_ptr(targets, "apply_dispatch_roster_torch")))
+
+    def apply_dispatch_roster_timed_torch(self, targets, arrive_min=None, counted=None):
+        """``apply_dispatch_roster_torch`` with the arrival minute and the counted flag of every entry
+        (``vds_apply_dispatch_roster_device_ex``): ``arrive_min`` / ``counted`` as in ``apply_dispatch_vehicles_timed_torch``, addressed
+        by roster position like ``targets``.  Only a mover's entries are read - not those of a negative target, nor those at or beyond
+        ``off[r, C]``."""
+        who = "apply_dispatch_roster_timed_torch"
+        am, ct = self._vehicle_times_ptrs(arrive_min, counted, who)
+        self._chk(self._lib.vds_apply_dispatch_roster_device_ex(self._h, self._vehicle_targets_ptr(targets, who), am, ct))
 
     def advance(self):
         self._chk(self._lib.vds_advance(self._h))
@@ -355,7 +383,8 @@ class BatchedDispatchEnv:
         self._chk(self._lib.vds_run(self._h, int(n_ticks)))
 
     def run_hooked(self, n_ticks: int, actions=None, policy_graph=None, idle_pre=True, idle_now=True, supply=True, cl_orders=True, inflight=False,
-                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None, vehicle_outcomes=False, roster=False, roster_targets=None, orders=False):
+                   outcomes=False, idle_heads=0, vehicle_planes=None, vehicle_targets=None, vehicle_outcomes=False, roster=False, roster_targets=None, orders=False,
+                   vehicle_arrive_min=None, vehicle_counted=None, roster_arrive_min=None, roster_counted=None):
         """``n_ticks`` slots of ``SimCity`` WITH the dispatch hook on the device as one graph launch (``vds_run_hooked``): per slot
         step -> the named observation planes into the block ``obs_torch`` returns (``outcomes=True``: also the slot's per-cluster
         order outcomes into the block ``outcomes_torch`` returns; ``idle_heads=L``: also the first ``L`` entries of every idle list
@@ -380,7 +409,11 @@ class BatchedDispatchEnv:
         dispatch of the slot would change the lists the positions refer to.  Both off again by a call without them.
         ``orders=True`` (``vds_run_hooked_orders``): every slot ``t`` also refreshes, before the policy, the rows of the orders it
         processed in the block ``orders_torch`` returns (range ``(t, t)``); the block accumulates over the day.  Capture the policy
-        against that tensor (or ``orders_device_ptr()``) taken before: the day uses that block.  Off again by a call without it."""
+        against that tensor (or ``orders_device_ptr()``) taken before: the day uses that block.  Off again by a call without it.
+        ``vehicle_arrive_min`` / ``vehicle_counted`` and ``roster_arrive_min`` / ``roster_counted`` (``vds_run_hooked_vehicles_ex`` /
+        ``vds_run_hooked_roster_ex``): the tensors of ``apply_dispatch_vehicles_timed_torch`` / ``apply_dispatch_roster_timed_torch``
+        that go with ``vehicle_targets`` / ``roster_targets`` (they need them), applied with them every slot.  Off again by a call
+        without them; switching them on or off re-builds the slot's dispatch node."""
         planes = (1 if idle_pre else 0) | (2 if idle_now else 0) | (4 if supply else 0) | (8 if cl_orders else 0) | (16 if inflight else 0)
         planes |= PLANE_OUTCOMES if outcomes else 0
         K, ptr = 0, None
@@ -394,14 +427,27 @@ class BatchedDispatchEnv:
         raw = None
         if policy_graph is not None:
             raw = policy_graph if isinstance(policy_graph, int) else int(policy_graph.raw_cuda_graph())
-        self._chk(self._lib.vds_run_hooked_idle_heads(self._h, int(idle_heads)))
         vt = None if vehicle_targets is None else self._vehicle_targets_ptr(vehicle_targets, "run_hooked")
-        self._chk(self._lib.vds_run_hooked_vehicles(self._h, self._vehicle_mask(vehicle_planes), vt))
+        vam, vct = self._vehicle_times_ptrs(vehicle_arrive_min, vehicle_counted, "run_hooked", ("vehicle_arrive_min", "vehicle_counted"))
+        ram, rct = self._vehicle_times_ptrs(roster_arrive_min, roster_counted, "run_hooked", ("roster_arrive_min", "roster_counted"))
+        if vt is None and (vam is not None or vct is not None):
+            raise Exception("run_hooked: vehicle_arrive_min / vehicle_counted need vehicle_targets")
+        if rt is None and (ram is not None or rct is not None):
+            raise Exception("run_hooked: roster_arrive_min / roster_counted need roster_targets")
+        self._chk(self._lib.vds_run_hooked_idle_heads(self._h, int(idle_heads)))
+        # (without the two tensors: the plain setter, which is the (..., NULL, NULL) case and switches them off again)
+        if vam is None and vct is None:
+            self._chk(self._lib.vds_run_hooked_vehicles(self._h, self._vehicle_mask(vehicle_planes), vt))
+        else:
+            self._chk(self._lib.vds_run_hooked_vehicles_ex(self._h, self._vehicle_mask(vehicle_planes), vt, vam, vct))
         self._chk(self._lib.vds_run_hooked_vehicle_outcomes(self._h, 1 if vehicle_outcomes else 0))
         self._chk(self._lib.vds_run_hooked_orders(self._h, 1 if orders else 0))
         if roster or roster_targets is not None or self._hooked_roster:
             # (the switch is only touched by a day that uses it, or to switch it off again)
-            self._chk(self._lib.vds_run_hooked_roster(self._h, 1 if roster else 0, rt))
+            if ram is None and rct is None:
+                self._chk(self._lib.vds_run_hooked_roster(self._h, 1 if roster else 0, rt))
+            else:
+                self._chk(self._lib.vds_run_hooked_roster_ex(self._h, 1 if roster else 0, rt, ram, rct))
             self._hooked_roster = bool(roster)
         self._chk(self._lib.vds_run_hooked(self._h, int(n_ticks), planes, K, ptr, C.c_void_p(raw) if raw is not None else None))
 
