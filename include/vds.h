@@ -702,6 +702,59 @@ int vds_restore_device(vds_handle *h, const void *dev_src_replica);
 int vds_snapshot_info(const vds_handle *h, int32_t *step, int32_t *stepped, int64_t *bytes);
 int vds_snapshot_drop(vds_handle *h);
 
+/* Policy-chosen matching: the handle runs Update by itself and commits an order-to-vehicle tensor the caller computed on the device -
+ * the body of a MatchFunction override (:900-975) that keeps the reference's bookkeeping and replaces only the search.
+ * vds_set_match_external(h, on != 0) makes h such a handle; vds_get_match_external returns 1 / 0.  Allowed between vds_create and
+ * vds_load_static (VDS_ESTATE afterwards).  Such a handle
+ *   - takes the wide state layout whatever vds_config.force_generic says, every arrival through the ring / far tables;
+ *   - refuses neighbor_can_server (VDS_EINVAL from the setter: the neighbour search is part of the built-in match);
+ *   - takes ONE order day: vds_load_order_days with n_days > 1, vds_load_orders_strided with a stride and vds_set_replica_days return
+ *     VDS_EINVAL;
+ *   - refuses vds_run and vds_run_hooked* (VDS_ESTATE): a day is stepped slot by slot;
+ *   - reports "k_update_external" from vds_main_kernel: vds_step launches UpdateFunction alone (arrivals join the idle lists,
+ *     idle_pre is taken, the slot's order count is 0 until the match) - the launch vds_profile_enable brackets.
+ * One slot is  vds_step -> (the policy reads whatever it likes) -> vds_apply_match_device -> dispatch calls of any form -> vds_advance.
+ * vds_apply_match_device: dev_assign is a device-resident int32 tensor [replicas][M], M = the most orders one slot of the loaded day
+ * processes (vds_match_orders_device); column j belongs to the j-th order the slot processes, in Order.ID order.  In replica r:
+ *     for j, order in enumerate(orders processed in this slot):                  # the cursor of :912-973, quirk Q1 included
+ *         self.OrderNum += 1;  NowCluster.Orders.append(order)                   # :917-919
+ *         v = dev_assign[r][j]
+ *         if v >= 0 and Vehicles[v] in Vehicles[v].Cluster.IdleVehicles and no order of this slot with a smaller ID named v:
+ *             wait = RoadCost(Vehicles[v].LocationNode, order.PickupPoint)       # :949-965 verbatim from here
+ *             order.PickupWaitTime = wait;  self.TotallyWaitTime += wait;  Vehicles[v].Orders.append(order)
+ *             Clusters[cluster of DeliveryPoint].VehiclesArrivetime[Vehicles[v]] = RealExpTime + wait + order.OrderValue
+ *             Vehicles[v].Cluster.IdleVehicles.remove(Vehicles[v]);  order.ArriveInfo = "Success"
+ *         else:
+ *             self.RejectNum += 1;  order.ArriveInfo = "Reject"                  # :944-945
+ *   - The vehicle may stand in any cluster.  The engine computes wait, arrival minute and value; the policy names the vehicle.
+ *   - PICKUPTIMEWINDOW (:943, vds_config.pickup_reject_threshold) is part of the search the policy replaces: it is NOT applied.
+ *   - Rejected, as documented behaviour and not as an error: a negative entry; a vehicle that is not idle (on its way, or at or beyond
+ *     the replica's fleet, vds_set_fleet); a vehicle an order of the slot with a smaller ID named.  The result rows
+ *     (vds_orders_device, vds_read_orders, vds_vehicle_outcomes_device, vds_outcomes_device) show the outcome.
+ *   - An entry >= vehicles is never used as an index: its order is rejected, the others are applied, and a sticky error of its own is
+ *     reported once by the next vds_sync / vds_read_* (VDS_ESTATE).
+ *   - The evaluations counter does not move.  Entries at or beyond the slot's order count are never read.  NULL rejects every order.
+ * Must follow vds_step of the slot (VDS_EINVAL otherwise) and is called exactly once per slot (VDS_ESTATE the second time), also in a
+ * slot without orders, where it launches nothing.  Until then vds_advance and every dispatch entry point of the slot return
+ * VDS_ESTATE: the reference runs Match before Dispatch, and an arrival dict lists a slot's order-carrying entries before its dispatched
+ * ones.  Between vds_step and the match the result rows of the slot's orders are undefined; afterwards the "slot stepped last" blocks
+ * show the policy's matches.  Asynchronous on the handle's stream, which must be ordered after the producer of the tensor; the tensor
+ * must stay alive until the stream has passed the call.  VDS_ESTATE on a handle that is not external.  Clears the idle roster's
+ * freshness flag.  The per-vehicle claim words the call works with (int32 [replicas][vehicles], allocated by the first call) are
+ * constant between calls: a snapshot ignores them and saves whether its slot had been matched.
+ * vds_match_orders_device: what the policy needs to know about the orders, static per loaded day (re-made by every vds_load_orders):
+ *   *dev_rec       int32 [Oq][4] {pickup node, delivery node, pickup cluster, OrderValue}; row i is Order.ID i (Oq processed orders);
+ *   *dev_slot_off  int32 [T + 1]: slot t processes ids slot_off[t] .. slot_off[t + 1] - 1; column j of dev_assign is id slot_off[t] + j;
+ *   *M             the width of dev_assign.
+ * vds_read_match_orders copies the two arrays to the host (either may be NULL; call with both NULL to size them: *n_orders = Oq,
+ * *n_slots = T).  Both: VDS_EINVAL before vds_load_orders, VDS_ESTATE on a handle that is not external.
+ * Out of scope: the dense layout, the day graphs and the Simulation shell. */
+int vds_set_match_external(vds_handle *h, int32_t on);
+int vds_get_match_external(const vds_handle *h);
+int vds_apply_match_device(vds_handle *h, const void *dev_assign);
+int vds_match_orders_device(vds_handle *h, void **dev_rec, void **dev_slot_off, int32_t *M);
+int vds_read_match_orders(vds_handle *h, int32_t *rec, int32_t *slot_off, int32_t *n_orders, int32_t *n_slots);
+
 /* As vds_reduce_counters, delivering the int64 [VDS_NUM_COUNTERS] totals of this handle's
  * replicas (raw device sums; VALUE_SUM = matched orders only) into caller-owned DEVICE memory,
  * asynchronously on the handle's stream - the send buffer of the cross-GPU RCCL all-reduce. */
@@ -778,7 +831,8 @@ const char *vds_cluster_cost_sums_error(void);
 
 /* Name of the kernel that vds_step launches for the main part of a tick with the handle's current tables (the one
  * vds_profile_enable brackets with events): "k_tick_dense", "k_tick_rows", "k_tick", "k_dfs_hybrid" (k_tick_rows in stamp mode +
- * k_dfs_walk), "k_tick_replica2" or "k_match_dfs".  Valid after vds_load_orders; static string. */
+ * k_dfs_walk), "k_tick_replica2" or "k_match_dfs" - or "k_update_external" on a handle with external matching (UpdateFunction alone:
+ * no match is part of it).  Valid after vds_load_orders; static string. */
 const char *vds_main_kernel(const vds_handle *h);
 
 /* Library/ABI version: (major << 16) | minor. */

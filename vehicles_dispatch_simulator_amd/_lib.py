@@ -101,6 +101,11 @@ SYMBOLS = {
     "vds_run_hooked_roster": (C.c_int, [_VP, _I32, _VP]),
     "vds_apply_dispatch_roster_device_ex": (C.c_int, [_VP, _VP, _VP, _VP]),
     "vds_run_hooked_roster_ex": (C.c_int, [_VP, _I32, _VP, _VP, _VP]),
+    "vds_set_match_external": (C.c_int, [_VP, _I32]),
+    "vds_get_match_external": (C.c_int, [_VP]),
+    "vds_apply_match_device": (C.c_int, [_VP, _VP]),
+    "vds_match_orders_device": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_I32)]),
+    "vds_read_match_orders": (C.c_int, [_VP, _VP, _VP, C.POINTER(_I32), C.POINTER(_I32)]),
     "vds_snapshot": (C.c_int, [_VP]),
     "vds_restore": (C.c_int, [_VP, _VP]),
     "vds_restore_device": (C.c_int, [_VP, _VP]),

@@ -244,7 +244,7 @@ struct vds_handle {
         unsigned gen = 0;                    // state_gen and the capacities the store was made for / the snapshot taken under
         int R = 0, C = 0, idle_cap = 0, ring_cap = 0, fl_cap = 0, H = 0, dense = 0, Oq = 0, arr_slots = 0;
         bool sup = false, arr = false;
-        int t = 0, last_stepped = -1, dispatch_seq = 0, seq_tick0 = 0, seq_tick = -1;
+        int t = 0, last_stepped = -1, dispatch_seq = 0, seq_tick0 = 0, seq_tick = -1, matched_tick = -1;
         int *d_map = nullptr;                // [R] the restore map in stored replica indices (host maps are uploaded here, device maps checked into it)
         // host maps are staged in two alternating pinned buffers, each guarded by an event recorded behind its upload: vds_restore waits
         // only for the upload of the restore before the last one, which has long finished - the call stays asynchronous
@@ -253,6 +253,12 @@ struct vds_handle {
         bool pin_used[2] = {false, false};
         int pin_i = 0;
     } snap;
+    // vds_set_match_external: the step is Update alone, the slot's matches come from vds_apply_match_device (vds_match_external.hip)
+    bool match_external = false;
+    int matched_tick = -1;                   // the slot whose vds_apply_match_device has been issued (-1: none since the clock was reset)
+    int *d_claim = nullptr;                  // int32 [S.R][V], INT_MAX between calls; made on the first vds_apply_match_device (in MEM_STATE)
+    int *d_match_rec = nullptr, *d_match_off = nullptr;      // vds_match_orders_device: int32 [Oq][4] / [T + 1] (in MEM_ORDERS), and their host copies
+    std::vector<int> match_rec, match_off;
     bool restored_episode = false;           // the episode continues from a snapshot: its slow-path statistics describe no whole day (adapt_dense)
 };
 
@@ -310,7 +316,7 @@ static void invalidate(vds_handle *h, unsigned changed) {
     h->roster_fresh = false;
 }
 // the episode clock back to the start of the day
-static void clock_reset(vds_handle *h) { h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1; h->roster_fresh = false; }
+static void clock_reset(vds_handle *h) { h->t = 0; h->last_stepped = -1; h->dispatch_seq = 0; h->seq_tick = -1; h->matched_tick = -1; h->roster_fresh = false; }
 
 // No C++ exception may cross the C ABI (vds.h: "never abort"): host allocation failures and the like become a
 // status code + vds_last_error.
@@ -457,11 +463,20 @@ static int ensure_block(vds_handle *h, T **p, size_t n, int fill) {
 // refusal): callable at all, nothing to do (n == 0, before the arguments are looked at), then the slot's sequence bookkeeping for the n
 // sequence numbers the call uses up.  *seq_base: the numbers the slot's earlier calls used; -1 with VDS_OK: nothing to do.  Whatever
 // is applied changes the lists: the roster is stale from here on.
+// external matching: the reference runs Match before Dispatch (:1079-1083), and the arrival keys order a slot's match entries before its
+// dispatch entries - so nothing of slot t but its match may follow its step until vds_apply_match_device has been issued
+static int match_pending(vds_handle *h, const char *fn) {
+    if (h->match_external && h->last_stepped == h->t && h->matched_tick != h->t)
+        return fail(h, VDS_ESTATE, "%s: external matching: slot %d has been stepped but not matched - call vds_apply_match_device first", fn, h->t);
+    return VDS_OK;
+}
+
 template <typename F>
 static int dispatch_begin(vds_handle *h, const char *fn, int n, F args, int *seq_base) {
     *seq_base = -1;
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "%s: call vds_reset first", fn);
     if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "%s: must follow vds_step of the current tick (the hook runs after Match, :1083)", fn);
+    { const int rcm = match_pending(h, fn); if (rcm) return rcm; }
     if (n == 0) return VDS_OK;
     const int rca = args();
     if (rca) return rca;
@@ -613,6 +628,7 @@ void vds_config_init(vds_config *cfg) {
 
 const char *vds_main_kernel(const vds_handle *h) {
     if (!h || !h->have_orders) return "";
+    if (h->match_external) return "k_update_external";      // (k_tick<false>: UpdateFunction alone - the matches come from vds_apply_match_device)
     if (!h->dfs_mode) return h->S.dense ? "k_tick_dense" : (h->S.fast_ok ? "k_tick_rows" : "k_tick");
     if (h->hybrid_ok && h->cfg.force_generic == 0 && h->S.dense_st) return "k_dfs_dense";       // (k_tick_dense in stamp form + k_dfs_walk on the dense layout)
     if (h->hybrid_ok && h->cfg.force_generic == 0) return "k_dfs_hybrid";                        // (k_tick_rows in stamp mode + the committing k_dfs_walk)
@@ -831,6 +847,7 @@ static int alloc_state(vds_handle *h, int O) {
     h->d_veh = nullptr;                                  // (and the per-vehicle planes)
     h->d_vout = nullptr;                                 // (and the per-vehicle outcomes)
     h->d_roster = nullptr; h->roster_fresh = false;      // (and the idle roster)
+    h->d_claim = nullptr;                                // (and the claim block of vds_apply_match_device)
     S.idle_cap = idle_cap; S.fl_cap = far_cap; S.in_cap = far_cap; S.H = H; S.ring_cap = ring_cap;
     const size_t B = (size_t)C * R;
     h->alloc_dense = S.dense; h->alloc_st = S.dense_st;
@@ -944,6 +961,7 @@ static int alloc_results(vds_handle *h) {
 static int set_replica_days_impl(vds_handle *h, const int32_t *replica_day) {
     if (!h || !h->have_orders) return fail(h, VDS_EINVAL, "vds_set_replica_days: load order days first");
     if (!replica_day) return fail(h, VDS_EINVAL, "vds_set_replica_days: null map");
+    if (h->match_external) return fail(h, VDS_EINVAL, "vds_set_replica_days: external matching takes one order day");
     const int n_days = h->S.n_days;
     for (int r = 0; r < h->R_ext; ++r)
         if (replica_day[r] < 0 || replica_day[r] >= n_days) return fail(h, VDS_EINVAL, "vds_set_replica_days: replica %d is mapped to day %d of %d", r, replica_day[r], n_days);
@@ -971,6 +989,7 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
     LoadTimer lt;
     if (!h || !h->have_static) return fail(h, VDS_EINVAL, "vds_load_orders: call vds_load_static first");
     if (n_days < 1 || !day_off || !release_min || !pickup || !delivery) return fail(h, VDS_EINVAL, "vds_load_orders: bad argument");
+    if (h->match_external && n_days > 1) return fail(h, VDS_EINVAL, "vds_load_order_days: external matching takes one order day (the assignment tensor's columns are the slot's orders of ONE day)");
     for (int d = 0; d < n_days; ++d)
         if (day_off[d + 1] - day_off[d] < 1 || day_off[d + 1] - day_off[d] > 0x7fffffff) return fail(h, VDS_EINVAL, "vds_load_orders: day %d has no orders (or more than 2^31)", d);
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1039,6 +1058,11 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
     }
     lt.lap("visit rows + bounds per order");
     { DayDesc *dd; if ((rc = upload(h, MEM_ORDERS, &dd, ddesc))) return rc; S.day = dd; }
+    h->d_match_rec = nullptr; h->d_match_off = nullptr;
+    if (h->match_external) {        // what a matching policy reads of the orders (vds_match_orders_device): static per loaded day
+        build_match_orders(ot, delivery, h->match_rec, h->match_off);
+        if ((rc = upload(h, MEM_ORDERS, &h->d_match_rec, h->match_rec)) || (rc = upload(h, MEM_ORDERS, &h->d_match_off, h->match_off))) return rc;
+    }
     // ---- dense layout (k_tick_dense: 4-byte idle entries, 8-byte arrival entries): the plain tick - one shared day, one day per
     //      workgroup chunk or one day per replica (day modes 0 / 1 / 2) -, ids that fit the packed keys.  vds_config.force_generic 5
     //      keeps the wide layout and k_tick_rows.
@@ -1082,6 +1106,7 @@ static int load_days_body(vds_handle *h, int32_t n_days, const int64_t *day_off,
         S.dense_force_slow = h->dbg_dense_slow & 1;
         S.pull = (S.dense && S.V < (1 << 24) - 1 && !(h->dbg_dense_slow & 2) && env_int("VDS_DENSE_PULL", 1) != 0) ? 1 : 0;
         if (S.dense_st && !S.pull) { S.dense = 0; S.dense_st = 0; }          // (the stamp form needs the static arrival slots)
+        if (h->match_external) { S.dense = 0; S.dense_st = 0; S.pull = 0; }  // (external matching: the wide layout, every arrival through the ring)
     }
     // ---- static arrival slots of the dense tick ("pull", vds_device.h): every processed order owns one u32 slot per replica in
     //      D.arr, in the order (destination cluster, earliest arrival slot a0, id); the destination bucket reads the slots of the
@@ -1160,6 +1185,7 @@ static int load_orders_strided_impl(vds_handle *h, const int32_t *release_min, c
                                     int64_t replica_stride) {
     if (!h) return VDS_EINVAL;
     if (replica_stride == 0) return load_orders_impl(h, release_min, pickup, delivery, O);
+    if (h->match_external) return fail(h, VDS_EINVAL, "vds_load_orders_strided: external matching takes one order day (replica_stride 0)");
     if (O < 1 || replica_stride < O) return fail(h, VDS_EINVAL, "vds_load_orders_strided: replica_stride must be 0 (shared day) or >= O");
     const int R = h->cfg.replicas;
     if (replica_stride == O) {
@@ -1673,6 +1699,19 @@ static int step_impl(vds_handle *h, bool flush = true) {
     h->roster_fresh = false;
     const bool hybrid = run_groups_hybrid(h), replica2 = h->dfs_mode && !hybrid && h->dfs2_ok && h->cfg.force_generic != 1;
     hipEvent_t a = nullptr, b = nullptr;
+    if (h->match_external) {
+        // Update alone (k_tick<false>): nothing is matched, so nothing is deferred either - no k_tick_work pass
+        if (h->profiling) {
+            a = next_event(h); b = next_event(h);
+            if (!a || !b) return fail(h, VDS_EHIP, "vds_step: hipEventCreate failed");
+            HIPCHK(h, hipEventRecord(a, h->stream));
+        }
+        launch_update_only(h->S, h->D, h->t, h->stream);
+        if (b) HIPCHK(h, hipEventRecord(b, h->stream));
+        HIPCHK(h, hipGetLastError());
+        h->last_stepped = h->t;
+        return VDS_OK;
+    }
     if (h->profiling && (!h->dfs_mode || hybrid || replica2)) {
         a = next_event(h); b = next_event(h);
         if (!a || !b) return fail(h, VDS_EHIP, "vds_step: hipEventCreate failed");
@@ -1700,6 +1739,7 @@ static int step_impl(vds_handle *h, bool flush = true) {
 int vds_advance(vds_handle *h) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_advance: call vds_reset first");
     if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_advance: tick %d has not been stepped", h->t);
+    { const int rcm = match_pending(h, "vds_advance"); if (rcm) return rcm; }
     h->t++;
     return VDS_OK;
 }
@@ -1781,6 +1821,7 @@ static int build_group_graph(vds_handle *h, int32_t n_ticks, int G, hipGraph_t *
 // tick over all replicas.
 int vds_run(vds_handle *h, int32_t n_ticks) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_run: call vds_reset first");
+    if (h->match_external) return fail(h, VDS_ESTATE, "vds_run: external matching: every slot needs its vds_apply_match_device - step slot by slot");
     h->roster_fresh = false;
     if (!run_graph_on(h) || h->profiling || n_ticks < 8 || h->last_stepped == h->t || h->t + n_ticks > h->S.T) return run_eager(h, n_ticks);
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1981,6 +2022,7 @@ static int run_hooked_eager(vds_handle *h, const HookPlan &p) {
 // the one it was built with (hook_built); another plan builds the slots anew - per slot every group's tick and observation half, the
 // policy, every group's dispatch nodes form by form - and puts them behind hook_exec (install_graph: in place where the shape is the same).
 static int run_hooked_impl(vds_handle *h, int32_t n_ticks, int32_t planes, int32_t K, const void *dev_actions, void *policy_graph) {
+    if (h && h->match_external) return fail(h, VDS_ESTATE, "vds_run_hooked: external matching: the day graph holds no match node yet - step slot by slot");
     HookPlan plan;
     const int rcp = hook_resolve(h, n_ticks, planes, K, dev_actions, policy_graph, &plan);
     if (rcp || plan.n == 0) return rcp;
@@ -2063,6 +2105,12 @@ int vds_sync(vds_handle *h) {
         const int keep = err[0] & ~ERR_DISPATCH;
         HIPCHK(h, hipMemcpy(h->D.err, &keep, sizeof(int), hipMemcpyHostToDevice));
         return fail(h, VDS_ESTATE, "dispatch of an idle position that does not exist (or listed twice); the action was skipped");
+    }
+    if (err[0] & ERR_MATCH) {
+        // the order was rejected, every other one was applied: consistent - reported once and cleared, like a refused dispatch
+        const int keep = err[0] & ~ERR_MATCH;
+        HIPCHK(h, hipMemcpy(h->D.err, &keep, sizeof(int), hipMemcpyHostToDevice));
+        return fail(h, VDS_ESTATE, "vds_apply_match_device: an assignment entry >= %d vehicles; its order was rejected", h->S.V);
     }
     if (err[0] & ERR_RESTORE) {
         // the replica kept its own snapshot row, every other one was restored: consistent - reported once and cleared, like a refused dispatch
@@ -2148,7 +2196,7 @@ static int snapshot_impl(vds_handle *h) {
     if (!snap_fits(h)) { const int rc = snap_alloc(h); if (rc) return rc; }
     const int rc = snap_copy(h, h->D, s.D, nullptr, h->last_stepped + 1);
     if (rc) return rc;
-    s.t = h->t; s.last_stepped = h->last_stepped; s.dispatch_seq = h->dispatch_seq; s.seq_tick0 = h->seq_tick0; s.seq_tick = h->seq_tick;
+    s.t = h->t; s.last_stepped = h->last_stepped; s.dispatch_seq = h->dispatch_seq; s.seq_tick0 = h->seq_tick0; s.seq_tick = h->seq_tick; s.matched_tick = h->matched_tick;
     s.valid = true;
     return VDS_OK;
 }
@@ -2163,7 +2211,7 @@ static int restore_finish(vds_handle *h, const int *user_dev_map, const int *map
     }
     const int rc = snap_copy(h, s.D, h->D, map, s.last_stepped + 1);
     if (rc) return rc;
-    h->t = s.t; h->last_stepped = s.last_stepped; h->dispatch_seq = s.dispatch_seq; h->seq_tick0 = s.seq_tick0; h->seq_tick = s.seq_tick;
+    h->t = s.t; h->last_stepped = s.last_stepped; h->dispatch_seq = s.dispatch_seq; h->seq_tick0 = s.seq_tick0; h->seq_tick = s.seq_tick; h->matched_tick = s.matched_tick;
     h->restored_episode = true;
     h->roster_fresh = false;
     return VDS_OK;
@@ -2243,6 +2291,7 @@ static int apply_dispatch_impl(vds_handle *h, int32_t n, const int32_t *replica,
                        const int32_t *counted = nullptr) {
     if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_apply_dispatch: call vds_reset first");
     if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_apply_dispatch: must follow vds_step of the current tick (the hook runs after Match, :1083)");
+    { const int rcm = match_pending(h, "vds_apply_dispatch"); if (rcm) return rcm; }
     if (n == 0) return VDS_OK;
     if (n < 0 || !replica || !from_cluster || !idle_pos || !target_node) return fail(h, VDS_EINVAL, "vds_apply_dispatch: bad argument");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -3096,6 +3145,63 @@ static int apply_dispatch_roster_device_impl(vds_handle *h, const void *dev_targ
     if (rc || seq_base < 0) return rc;
     Chain(h->stream).add(emit_dispatch_roster, h->S, h->D, h->t, (const int *)dev_targets, roster_off(h), (const int *)arrive, (const int *)counted, seq_base, 0, 0);
     HIPCHK(h, hipGetLastError());
+    return VDS_OK;
+}
+
+// ---- external matching (vds_match_external.hip; include/vds.h has the contract)
+int vds_set_match_external(vds_handle *h, int32_t on) {
+    if (!h) return VDS_EINVAL;
+    if (h->have_static) return fail(h, VDS_ESTATE, "vds_set_match_external: the static tables are loaded - set it between vds_create and vds_load_static");
+    if (on && h->cfg.neighbor_can_server) return fail(h, VDS_EINVAL, "vds_set_match_external: neighbor_can_server is set - the neighbour search is part of the built-in match");
+    h->match_external = on != 0;
+    return VDS_OK;
+}
+int vds_get_match_external(const vds_handle *h) { return h ? (h->match_external ? 1 : 0) : VDS_EINVAL; }
+
+static int apply_match_device_impl(vds_handle *h, const void *dev_assign) {
+    if (!h || !h->have_reset) return fail(h, VDS_EINVAL, "vds_apply_match_device: call vds_reset first");
+    if (!h->match_external) return fail(h, VDS_ESTATE, "vds_apply_match_device: the handle matches by itself (vds_set_match_external before vds_load_static)");
+    if (h->last_stepped != h->t) return fail(h, VDS_EINVAL, "vds_apply_match_device: must follow vds_step of the current slot (Match runs behind Update, :1079)");
+    if (h->matched_tick == h->t) return fail(h, VDS_ESTATE, "vds_apply_match_device: slot %d has been matched already (once per slot)", h->t);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int n = h->match_off[h->t + 1] - h->match_off[h->t];
+    if (n > 0) {
+        const size_t words = std::max<size_t>((size_t)h->S.R * h->S.V, 1);
+        if (!h->d_claim) {
+            const int rc = dev_alloc(h, MEM_STATE, &h->d_claim, words);
+            if (rc) { h->d_claim = nullptr; return rc; }
+            HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->d_claim, 0x7FFFFFFF, words, h->stream));
+        }
+        const int M = h->S.max_tick_orders;
+        Chain c(h->stream);
+        c.add(emit_match_claim, h->S, h->D, h->t, n, (const int *)dev_assign, M, h->d_claim);
+        c.add(emit_match_walk, h->S, h->D, h->t, h->d_claim);
+        c.add(emit_match_finish, h->S, h->D, h->t, (const int *)dev_assign, M, h->d_claim);
+        HIPCHK(h, hipGetLastError());
+    }
+    h->matched_tick = h->t;
+    h->roster_fresh = false;
+    return VDS_OK;
+}
+int vds_apply_match_device(vds_handle *h, const void *dev_assign) {
+    return guarded(h, "vds_apply_match_device", [&] { return apply_match_device_impl(h, dev_assign); });
+}
+
+int vds_match_orders_device(vds_handle *h, void **dev_rec, void **dev_slot_off, int32_t *M) {
+    if (!h || !h->have_orders) return fail(h, VDS_EINVAL, "vds_match_orders_device: load the orders first");
+    if (!h->match_external) return fail(h, VDS_ESTATE, "vds_match_orders_device: the handle matches by itself (vds_set_match_external before vds_load_static)");
+    if (dev_rec) *dev_rec = h->d_match_rec;
+    if (dev_slot_off) *dev_slot_off = h->d_match_off;
+    if (M) *M = h->S.max_tick_orders;
+    return VDS_OK;
+}
+int vds_read_match_orders(vds_handle *h, int32_t *rec, int32_t *slot_off, int32_t *n_orders, int32_t *n_slots) {
+    if (!h || !h->have_orders) return fail(h, VDS_EINVAL, "vds_read_match_orders: load the orders first");
+    if (!h->match_external) return fail(h, VDS_ESTATE, "vds_read_match_orders: the handle matches by itself (vds_set_match_external before vds_load_static)");
+    if (rec) std::copy(h->match_rec.begin(), h->match_rec.end(), rec);
+    if (slot_off) std::copy(h->match_off.begin(), h->match_off.end(), slot_off);
+    if (n_orders) *n_orders = (int32_t)(h->match_rec.size() / 4);
+    if (n_slots) *n_slots = (int32_t)h->match_off.size() - 1;
     return VDS_OK;
 }
 

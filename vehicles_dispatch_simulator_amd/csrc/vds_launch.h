@@ -86,6 +86,15 @@ void emit_orders_block(const Emit &e, const Static &S, const State &D, int slot_
 void emit_dispatch_vehicles(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *arrive, const int *counted, int seq_base, int r_lo, int r_n);
 // targets: int32 [R_ext][V] target node per roster entry (negative: stay), against the offsets `off` of the refresh it was written for
 void emit_dispatch_roster(const Emit &e, const Static &S, const State &D, int t, const int *targets, const int *off, const int *arrive, const int *counted, int seq_base, int r_lo, int r_n);
+// ---- vds_match_external.hip: the three launches of vds_apply_match_device, over all replicas
+// assign: int32 [R_ext][M] vehicle per order of the slot, in Order.ID order (null: every order rejected); claim: int32 [S.R][V], INT_MAX
+// everywhere before and after the three; n_orders: orders the slot processes (sizes the claim grid)
+enum { MATCH_CLAIM_THREADS = 256 };
+// sticky device error bit (err[0], next to the ERR_* of vds_device.h): an assignment entry >= V
+enum { ERR_MATCH = 64 };
+void emit_match_claim(const Emit &e, const Static &S, const State &D, int t, int n_orders, const int *assign, int M, int *claim);
+void emit_match_walk(const Emit &e, const Static &S, const State &D, int t, int *claim);
+void emit_match_finish(const Emit &e, const Static &S, const State &D, int t, const int *assign, int M, int *claim);
 // ---- vds_idle_roster.hip
 // planes: int32 [3][R_ext][V] {veh, node, cluster} by roster position, off: int32 [R_ext][C + 1]; one kernel writes every element of both
 // (dynamic LDS: idle_roster_lds, (C + 1) ints - C <= IDLE_ROSTER_C_MAX)

@@ -108,6 +108,9 @@ int build_order_tables(const CityView &city, int n_days, const int64_t *day_off,
 std::vector<int> build_order_ranks(const OrderTables &ot, int threads);
 std::vector<int> build_first_buckets(const OrderTables &ot, int threads);
 
+// the order block of vds_match_orders_device for day 0: rec int32 [Oq][4] by Order.ID, slot_off int32 [T + 1]; delivery: the day's array as loaded
+void build_match_orders(const OrderTables &ot, const int32_t *delivery, std::vector<int> &rec, std::vector<int> &slot_off);
+
 // ---- static arrival slots of the dense tick ("pull", vds_device.h)
 struct PullTables {
     bool ok = false;                         // the verdict: false - the dense tick keeps the arrival ring (nothing below is to be used)

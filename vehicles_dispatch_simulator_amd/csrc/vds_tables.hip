@@ -361,6 +361,22 @@ std::vector<int> build_order_ranks(const OrderTables &ot, int threads) {
     return so_rank;
 }
 
+// What a matching policy needs to know about the orders of day 0 (vds_match_orders_device): rec[i] = {pickup node, delivery node, pickup
+// cluster, OrderValue} of Order.ID i (the processed orders are a prefix of the ids), slot_off[t] = first id slot t processes
+void build_match_orders(const OrderTables &ot, const int32_t *delivery, std::vector<int> &rec, std::vector<int> &slot_off) {
+    const DayDesc &de = ot.ddesc[0];
+    const int a0 = ot.tick_off[de.tick_base];
+    slot_off.assign((size_t)de.T + 1, 0);
+    for (int t = 0; t <= de.T; ++t) slot_off[t] = ot.tick_off[de.tick_base + t] - a0;
+    rec.assign((size_t)4 * de.Oq, 0);
+    for (int i = 0; i < de.Oq; ++i) {
+        const int q = ot.ord_q[a0 + i];
+        const int4 r = ot.so_rec[q];
+        int *w = rec.data() + (size_t)4 * i;
+        w[0] = ot.so_pnode[q]; w[1] = delivery[r.x]; w[2] = (int)((unsigned)r.z >> 16); w[3] = r.w;
+    }
+}
+
 std::vector<int> build_first_buckets(const OrderTables &ot, int threads) {
     std::vector<int> so_bkt0(ot.n_rec, 0);
     const int C = ot.C;

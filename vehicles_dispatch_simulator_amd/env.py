@@ -65,7 +65,7 @@ class BatchedDispatchEnv:
                  depth_limit: int = 0, neighbor_can_server: bool = False, tick_minutes: int = 10,
                  reject_threshold: int = PICKUP_REJECT_THRESHOLD, device: int = 0,
                  idle_cap: int = 0, ring_cap: int = 0, ring_ticks: int = 0, far_cap: int = 0,
-                 force_generic: bool = False, stream: Optional[int] = None, dense_debug=None):
+                 force_generic: bool = False, stream: Optional[int] = None, dense_debug=None, match_external: bool = False):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         cfg = _lib.VdsConfig()
@@ -93,6 +93,11 @@ class BatchedDispatchEnv:
         self.R, self.V = int(replicas), int(vehicles)
         self.device = int(device)
         self.node2cluster = node2cluster
+        # the handle runs Update alone and commits the caller's order-to-vehicle tensor (vds_set_match_external): apply_match_torch
+        self.match_external = bool(match_external)
+        self.match_width = 0                     # M: columns of the assignment tensor (known once the orders are loaded)
+        if self.match_external:
+            self._chk(self._lib.vds_set_match_external(self._h, 1))
         if stream is not None:
             self.set_stream(stream)              # (an integer hipStream_t, or "legacy": see set_stream)
         if dense_debug is not None:       # test hook: (lanes per replica, idle entries / arrivals the fast path takes, force slow path)
@@ -138,6 +143,7 @@ class BatchedDispatchEnv:
         t = C.c_int32()
         self._chk(self._lib.vds_num_ticks(self._h, C.byref(t)))
         self.T = t.value
+        self._match_loaded()
 
     def load_order_days(self, days, replica_day=None):
         """Per-replica order days (``vds_load_order_days``): ``days`` is a sequence of ``(release_min, pickup,
@@ -186,6 +192,7 @@ class BatchedDispatchEnv:
         t = C.c_int32()
         self._chk(self._lib.vds_num_ticks(self._h, C.byref(t)))
         self.T = t.value
+        self._match_loaded()
 
     def replica_ticks(self, replica: int):
         """(ticks, orders) of the day ``replica`` replays."""
@@ -334,6 +341,57 @@ class BatchedDispatchEnv:
         who = "apply_dispatch_roster_timed_torch"
         am, ct = self._vehicle_times_ptrs(arrive_min, counted, who)
         self._chk(self._lib.vds_apply_dispatch_roster_device_ex(self._h, self._vehicle_targets_ptr(targets, who), am, ct))
+
+    def apply_match_torch(self, assign):
+        """The slot's matches from a policy (``vds_apply_match_device``; an env made with ``match_external=True``): ``assign`` is a
+        contiguous int32 CUDA tensor ``[R, match_width]`` on the handle's device, ``assign[r, j]`` the vehicle that serves the ``j``-th
+        order the slot processes in ``Order.ID`` order (id ``slot_off[t] + j``, ``match_orders_torch``) - or ``None``: every order is
+        rejected.  The engine computes wait, arrival minute and value (``simulator.py:949-965``); the pickup window is not applied.
+        Rejected, not errors: a negative entry, a vehicle that is not idle (or beyond the replica's fleet), a vehicle an order with a
+        smaller id named.  An entry ``>= V`` rejects its order and raises once at the next ``sync`` / read.  Columns at or beyond the
+        slot's order count are never read.  Once per slot, after ``step()`` and before any dispatch call and ``advance()``.
+        Asynchronous, no host copy; the tensor must stay alive until the handle's stream has passed the call and must have been
+        produced on (or synchronised with) that stream."""
+        if assign is None:
+            self._chk(self._lib.vds_apply_match_device(self._h, None))
+            return
+        who = "apply_match_torch"
+        if not hasattr(assign, "data_ptr") or not hasattr(assign, "is_cuda"):
+            raise Exception("%s: expected a torch tensor or None, got %s" % (who, type(assign).__name__))
+        if tuple(assign.shape) != (self.R, self.match_width):
+            raise Exception("%s: expected an int32 tensor [R, match_width] = [%d, %d], got %s" % (who, self.R, self.match_width, list(assign.shape)))
+        if str(assign.dtype) != "torch.int32" or not assign.is_cuda or not assign.is_contiguous():
+            raise Exception("%s: expected a contiguous int32 CUDA tensor" % who)
+        if assign.device.index is not None and assign.device.index != self.device:
+            raise Exception("%s: the tensor lives on cuda:%d, the handle on cuda:%d" % (who, assign.device.index, self.device))
+        self._chk(self._lib.vds_apply_match_device(self._h, C.c_void_p(assign.data_ptr())))
+
+    def _match_loaded(self):
+        if self.match_external:
+            m = C.c_int32()
+            self._chk(self._lib.vds_match_orders_device(self._h, None, None, C.byref(m)))
+            self.match_width = m.value
+
+    def _match_sizes(self):
+        n, t = C.c_int32(), C.c_int32()
+        self._chk(self._lib.vds_read_match_orders(self._h, None, None, C.byref(n), C.byref(t)))
+        return n.value, t.value
+
+    def match_orders_torch(self):
+        """What a matching policy needs to know about the orders (``vds_match_orders_device``), as zero-copy ``torch`` int32 views:
+        ``rec`` ``[Oq, 4]`` = ``{pickup node, delivery node, pickup cluster, OrderValue}`` of ``Order.ID == i`` (the processed orders),
+        ``slot_off`` ``[T + 1]``: slot ``t`` processes ids ``slot_off[t] .. slot_off[t + 1] - 1``.  Static until the next order load."""
+        pr, po = C.c_void_p(), C.c_void_p()
+        self._chk(self._lib.vds_match_orders_device(self._h, C.byref(pr), C.byref(po), None))
+        n, t = self._match_sizes()
+        return {"rec": _device_tensor(pr.value, (n, 4), "<i4", self.device), "slot_off": _device_tensor(po.value, (t + 1,), "<i4", self.device)}
+
+    def match_orders(self) -> Dict[str, np.ndarray]:
+        """``match_orders_torch`` as host arrays (``vds_read_match_orders``)."""
+        n, t = self._match_sizes()
+        rec, off = np.empty((n, 4), dtype=np.int32), np.empty(t + 1, dtype=np.int32)
+        self._chk(self._lib.vds_read_match_orders(self._h, _p(rec), _p(off), None, None))
+        return {"rec": rec, "slot_off": off}
 
     def advance(self):
         self._chk(self._lib.vds_advance(self._h))
