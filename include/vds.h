@@ -839,7 +839,7 @@ const char *vds_main_kernel(const vds_handle *h);
 int32_t vds_version(void);
 
 /* Which sources this binary was built from: "src:<kernels>+<host>" - the first 12 hex digits of the sha1 over the KERNEL sources of
- * csrc/ (the .hip kernel files, vds_kernels_common.h, vds_device.h) and the first 8 of the sha1 over the host side (vds_api.hip,
+ * csrc/ (the .hip kernel files, vds_kernels_common.h, vds_device.h) and the first 8 of the sha1 over the host side (the vds_api*.hip units,
  * vds.h); `make -C vehicles_dispatch_simulator_amd/csrc srchash` prints the same for a checkout, `make kernelhash` the kernel half
  * (what the committed rocprofv3 figures are keyed by: they survive host-only edits).  Instrumented builds append "+prof" / "+dbg" /
  * "+canary" / "+dirty".  bench.py prints it and compares it with the build the

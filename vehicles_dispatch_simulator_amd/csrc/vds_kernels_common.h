@@ -13,7 +13,7 @@ namespace vds {
 #define WORK_FULL 0x80000000u
 
 // Instrumented build only (make prof): timing-only ablation switches (results are INVALID when non-zero) and per-wave,
-// per-section cycle sums.  Each translation unit owns its copy; vds_api.hip sets / sums them all (VDS_PROF_ACCESSORS).
+// per-section cycle sums.  Each translation unit owns its copy; vds_api_debug.hip sets / sums them all (VDS_PROF_ACCESSORS).
 #define PROF_WAVES (1 << 16)
 #define PROF_SLOTS 32
 #ifdef VDS_PROF

@@ -1,5 +1,5 @@
-// Host-side launchers of the kernel files, as vds_api.hip calls them: declarations, and fleet_size (included by vds_api.hip and by
-// every file that defines one of them; hashed with the HOST sources: Makefile).
+// Host-side launchers of the kernel files, as the host units (vds_api*.hip) call them: declarations, and fleet_size (included by
+// vds_handle.h and by every file that defines one of them; hashed with the HOST sources: Makefile).
 //   launch_*  on a stream (the tick files only: the derived blocks and the tensor dispatch forms have no such twin)
 //   emit_*    on a stream or as a kernel node of an explicitly built hipGraph (Emit, vds_device.h), for the replicas
 //             [r_lo, r_lo + r_n) - r_lo a multiple of 16; r_n <= 0 (with r_lo 0): all.  One kernel each: which kernels refresh a

@@ -1,4 +1,4 @@
-// Device memory of libvds (host code: vds_api.hip, mem_check.cpp): every device block the library obtains for a handle comes from
+// Device memory of libvds (host code: the vds_api*.hip units through vds_handle.h, mem_check.cpp): every device block the library obtains for a handle comes from
 // dev_raw_alloc and goes back through dev_free - with guard zones in the guarded build, the fill in the dirty build and the count of
 // live blocks behind vds_debug_device_blocks - and belongs to exactly one DevGroup, named where it is allocated.
 #pragma once
